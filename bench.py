@@ -2,6 +2,7 @@
 """bench.py — FFC-DCGAN generator forward throughput on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload gen64|fgan128|fgan128sn|gan64train|fgan128train|block]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 `--gpus N` without a launcher (WORLD_SIZE unset) starts the N ranks itself
@@ -17,21 +18,28 @@ use batch statistics), synthetic z ~ N(0,1), weights from the reference's weight
 One step = one generator forward over one batch; inputs resident in HBM.
 
 Scaling (``--scaling``, default strong): the configuration's batch split over the ranks, with the
-weak-scaling figure alongside at N > 1.  ``--scaling weak``: every GPU runs the configuration's batch (gen64 256,
+weak-scaling figure alongside at N > 1 (``--full``).  ``--scaling weak``: every GPU runs the configuration's batch (gen64 256,
 fgan128 512 = configs[3], fgan128sn 1024 = configs[4]); the job's global batch is N x that, drawn
 once from one seed and sliced per rank, and train-mode BN normalises over ALL of it (SyncBN: the
 BN moments are all-reduced over RCCL, so the sharded result equals the global-batch forward; the
 strong split does the same over the configuration's batch).  The per-rank shard steps and the
 strong-scaling budget are in DESIGN.md §5.  One process per GPU; weights are
 broadcast once at init.  The step is hipGraph-captured (thread-local capture, the RCCL
-all-reduces inside the graph; graphs.py).  At N > 1 the gen64 line also carries the gathered
+all-reduces inside the graph; graphs.py).  At N > 1 the gen64 ``--full`` line also carries the gathered
 global-batch output's parity against the CPU reference.
 
-The JSON line also carries:
+A plain run sets up, warms up, times exactly ``--steps`` steps, writes the last timed step's outputs
+(``--dump-outputs DIR``: what a caller of the timed path receives, as DIR/<name>.npy in float32, at
+most 64 MB in all; a larger output is a fixed seeded sample of its batch rows) and prints one JSON
+line: metric, value, unit, ms_per_step (wall-clock milliseconds per timed step), dtype, config.
+The inputs and weights come from fixed seeds, so two runs with the same arguments see the same data.
+
+With ``--full`` the JSON line also carries (each takes GPU or CPU runs of its own after the timed steps):
   roofline      live per-kernel HIP-event timing of one eager pass (dominant kernel), MFMA f32 peak
   cpu_baseline  the oracle's fp32 op-for-op torch CPU path (oracle/ffc_oracle.py, fft="torch"),
                 rank 0 at N=1 only, bounded sample
   parity        normwise max|GPU - CPU reference| / max|CPU reference| for the same z and weights
+  weak_scaling  at N > 1 with --scaling strong: the weak-scaling measurement beside the strong split
 """
 from __future__ import annotations
 
@@ -92,7 +100,8 @@ def profile_pass(step, n):
 def time_steps(run, steps, world=1):
     """Time EXACTLY ``steps`` calls of ``run`` between a barrier + device synchronise on both sides
     (wall clock, max over ranks), with a HIP event after every step on the launch stream for the
-    per-step median (SURVEY.md §8d asks for the median).  -> (elapsed_s, median_ms_per_step)"""
+    per-step median (SURVEY.md §8d asks for the median).
+    -> (elapsed_s, median_ms_per_step, what the last call of ``run`` returned)"""
     import torch.distributed as dist
     evs = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
     if world > 1:
@@ -100,8 +109,9 @@ def time_steps(run, steps, world=1):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     evs[0].record()
+    out = None
     for i in range(steps):
-        run()
+        out = run()
         evs[i + 1].record()
     torch.cuda.synchronize()
     if world > 1:
@@ -114,7 +124,30 @@ def time_steps(run, steps, world=1):
                          dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, med = float(t[0]), float(t[1])
-    return elapsed, med
+    return elapsed, med, out
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files of one run together
+
+
+def dump_outputs(path, named, rank=0, world=1):
+    """--dump-outputs: write the last timed step's outputs, ``named`` = {name: tensor}, as
+    <path>/<name>.npy (float32; at N > 1 every rank writes its shard as <name>_rank<r>.npy).  The
+    byte budget is shared evenly; an output over its share is cut to a fixed seeded sample of its
+    batch rows (the same rows in every run: sorted first rows of a seed-0 permutation)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(named))
+    for name, t in named.items():
+        t = t.detach().float()
+        if t.numel() * 4 > share:
+            keep = share // (4 * t[0].numel())
+            if keep < 1:
+                raise SystemExit(f"--dump-outputs: one row of {name} exceeds the {share}-byte share")
+            rows = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.index_select(0, rows.to(t.device))
+        fn = name if world == 1 else f"{name}_rank{rank}"
+        np.save(os.path.join(path, fn + ".npy"), t.cpu().contiguous().numpy())
 
 
 def parse():
@@ -133,17 +166,25 @@ def parse():
     p.add_argument("--gpus", type=int, default=None,
                    help="number of GPUs / ranks (default: WORLD_SIZE, or 1); starts the ranks itself when "
                         "WORLD_SIZE is unset")
-    p.add_argument("--steps", type=int, default=200)
+    p.add_argument("--steps", type=int, default=200, help="timed steps (exactly this many)")
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--scaling", choices=["strong", "weak"], default="strong",
                    help="strong (default): the configuration's batch (gen64 256, fgan128 512, fgan128sn 1024) "
-                        "split over the ranks, as BASELINE configs[3]/[4] shard it; at N > 1 the line also "
-                        "carries the weak-scaling measurement (every GPU runs the configuration's batch) in "
+                        "split over the ranks, as BASELINE configs[3]/[4] shard it; at N > 1 with --full the line "
+                        "also carries the weak-scaling measurement (every GPU runs the configuration's batch) in "
                         "'weak_scaling'.  weak: only that measurement")
     p.add_argument("--global-batch", type=int, default=None,
                    help="strong scaling global batch (gen64: 256, fgan128: 512, fgan128sn: 1024)")
     p.add_argument("--batch", type=int, default=None, help="weak scaling samples per GPU (gen64: 256, "
                                                            "fgan128: 512, fgan128sn: 1024)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last of them computed as DIR/<name>.npy (float32, at "
+                        "most 64 MB in all; larger outputs as a fixed seeded sample of their batch rows)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure and check everything else the line can carry: the "
+                        "per-kernel roofline pass, the CPU baseline, parity against the CPU reference, and at "
+                        "N > 1 the weak-scaling figure (--cpu-seconds, --no-cpu-baseline, --profile-steps apply "
+                        "here)")
     p.add_argument("--dry-run", action="store_true",
                    help="launch + shard plan only, over gloo on the CPU (no GPU touched): rank 0 prints the plan")
     p.add_argument("--nz", type=int, default=100)
@@ -311,8 +352,31 @@ def train_main(args):
             run = graph.replay
     for _ in range(max(1, args.warmup)):
         run()
-    elapsed, med = time_steps(run, args.steps)
+    elapsed, med, last = time_steps(run, args.steps)
     value = args.batch * args.steps / elapsed
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": graph.ffc_output if use_graph else last})
+    extras = {}
+    if args.full:
+        extras = train_extras(args, step, F, cpu_state, z_cpu, dev)
+    line = {
+        "metric": "FFC-DCGAN G+D fwd+bwd train step images/sec @ B=256 64x64x3 (BASELINE configs[2])",
+        "value": round(value, 1), "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "ms_per_step_median": round(med, 4),
+        "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic: z ~ N(0,1); weights per fgan64_complete.py:22-31 weights_init",
+        "config": {"workload": f"FFCGenerator(nz={args.nz},nc={args.nc},ngf={args.ngf}) + FFCDiscriminator("
+                               f"nc={args.nc},ndf={args.ngf}) fwd+bwd + Adam, loss = mean(D(G(z)))",
+                   "global_batch": args.batch, "per_gpu_batch": args.batch, "bn_mode": "train", "hipgraph": use_graph,
+                   "parallelism": "dp1"},
+        "full": args.full, **extras,
+    }
+    print(json.dumps(line))
+
+
+def train_extras(args, step, F, cpu_state, z_cpu, dev):
+    """gan64train --full: the instrumented eager pass, the CPU baseline and the loss parity."""
     summ, _ = profile_pass(step, args.profile_steps)
     nprof = max(1, args.profile_steps)
     kernels = {k: {"launches_per_step": v["launches"] / nprof, "ms_per_step": v["ms"] / nprof,
@@ -363,20 +427,7 @@ def train_main(args):
         parity = {"loss_rel_err_vs_fp64_oracle": abs(got - ref) / abs(ref), "mode": f"train, B={nb}",
                   "gradients": "layer-wise vs the fp64 oracle in tests/test_gpu_train.py (<= 1e-4 normwise)",
                   "tolerance": 1e-4}
-    line = {
-        "metric": "FFC-DCGAN G+D fwd+bwd train step images/sec @ B=256 64x64x3 (BASELINE configs[2])",
-        "value": round(value, 1), "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "ms_per_step_median": round(med, 4),
-        "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic: z ~ N(0,1); weights per fgan64_complete.py:22-31 weights_init",
-        "config": {"workload": f"FFCGenerator(nz={args.nz},nc={args.nc},ngf={args.ngf}) + FFCDiscriminator("
-                               f"nc={args.nc},ndf={args.ngf}) fwd+bwd + Adam, loss = mean(D(G(z)))",
-                   "global_batch": args.batch, "per_gpu_batch": args.batch, "bn_mode": "train", "hipgraph": use_graph,
-                   "parallelism": "dp1"},
-        "roofline": roof, "cpu_baseline": cpu, "parity": parity, "kernels": kernels,
-    }
-    print(json.dumps(line))
+    return {"roofline": roof, "cpu_baseline": cpu, "parity": parity, "kernels": kernels}
 
 
 def fgan128train_main(args):
@@ -428,21 +479,27 @@ def fgan128train_main(args):
             run = graph.replay
     for _ in range(max(1, args.warmup)):
         run()
-    elapsed, med = time_steps(run, args.steps)
+    elapsed, med, last = time_steps(run, args.steps)
     value = B * args.steps / elapsed
-    summ, _ = profile_pass(step, args.profile_steps)
-    nprof = max(1, args.profile_steps)
-    kernels = {k: {"launches_per_step": v["launches"] / nprof, "ms_per_step": v["ms"] / nprof,
-                   "avg_us": 1e3 * v["ms"] / v["launches"]} for k, v in summ.items()}
-    mm = {k: v for k, v in summ.items() if v["flops"] > 0}
-    dom = max(mm, key=lambda k: mm[k]["ms"])
-    achieved = summ[dom]["flops"] / (summ[dom]["ms"] * 1e-3) / 1e12
-    roof = mfma_roof(dom, achieved)
-    tr = pmc_traffic(dom, args.workload)
-    roof["traffic"] = tr["bytes_per_launch"] if tr else None
-    cpu = parity = None
-    if not args.no_cpu_baseline:
-        cpu, parity = fgan128train_cpu(args, cpu_state, dev)
+    if args.dump_outputs:
+        loss_G, loss_D = graph.ffc_output if use_graph else last
+        dump_outputs(args.dump_outputs, {"loss_G": loss_G, "loss_D": loss_D})
+    extras = {}
+    if args.full:
+        summ, _ = profile_pass(step, args.profile_steps)
+        nprof = max(1, args.profile_steps)
+        kernels = {k: {"launches_per_step": v["launches"] / nprof, "ms_per_step": v["ms"] / nprof,
+                       "avg_us": 1e3 * v["ms"] / v["launches"]} for k, v in summ.items()}
+        mm = {k: v for k, v in summ.items() if v["flops"] > 0}
+        dom = max(mm, key=lambda k: mm[k]["ms"])
+        achieved = summ[dom]["flops"] / (summ[dom]["ms"] * 1e-3) / 1e12
+        roof = mfma_roof(dom, achieved)
+        tr = pmc_traffic(dom, args.workload)
+        roof["traffic"] = tr["bytes_per_launch"] if tr else None
+        cpu = parity = None
+        if not args.no_cpu_baseline:
+            cpu, parity = fgan128train_cpu(args, cpu_state, dev)
+        extras = {"roofline": roof, "cpu_baseline": cpu, "parity": parity, "kernels": kernels}
     line = {
         "metric": f"fgan128 G+D training iteration images/sec @ B={B} 128x128x3 (fgan128_complete.py:680-703)",
         "value": round(value, 1), "unit": "images/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -453,7 +510,7 @@ def fgan128train_main(args):
         "config": {"workload": "FGenerator(z=128) + spectral-norm Discriminator: generator update + 1 discriminator "
                                "update, hinge losses, AdamW", "global_batch": B, "per_gpu_batch": B,
                    "bn_mode": "train", "hipgraph": use_graph, "parallelism": "dp1"},
-        "roofline": roof, "cpu_baseline": cpu, "parity": parity, "kernels": kernels,
+        "full": args.full, **extras,
     }
     print(json.dumps(line))
 
@@ -564,8 +621,28 @@ def block_main(args):
             run = graph.replay
     for _ in range(max(1, args.warmup)):
         run()
-    elapsed, med = time_steps(run, args.steps)
+    elapsed, med, last = time_steps(run, args.steps)
     value = B * args.steps / elapsed
+    if args.dump_outputs:
+        out_l, out_g = graph.ffc_output if use_graph else last
+        dump_outputs(args.dump_outputs, {"out_local": out_l, "out_global": out_g})
+    extras = {}
+    if args.full:
+        extras = block_extras(args, step, blk, cpu_state, x_cpu, B)
+    print(json.dumps({
+        "metric": "FFC_BN_ACT(32->32, k3, 0.5/0.5, BN, ReLU) fwd samples/sec @ B=16 32x32 (BASELINE configs[0])",
+        "value": round(value, 1), "unit": "samples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "ms_per_step_median": round(med, 4),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic: x ~ N(0,1); weights per fgan64_complete.py:22-31 weights_init",
+        "config": {"workload": "FFC_BN_ACT(32,32,3,0.5,0.5,stride=1,padding=1,BatchNorm2d,ReLU) forward 32x32",
+                   "global_batch": B, "per_gpu_batch": B, "bn_mode": args.bn_mode, "hipgraph": use_graph,
+                   "parallelism": "dp1"},
+        "full": args.full, **extras}))
+
+
+def block_extras(args, step, blk, cpu_state, x_cpu, B):
+    """block --full: the instrumented eager pass, the CPU baseline and the parity against it."""
     summ, _ = profile_pass(step, args.profile_steps)
     nprof = max(1, args.profile_steps)
     kernels = {k: {"launches_per_step": v["launches"] / nprof, "ms_per_step": v["ms"] / nprof,
@@ -599,16 +676,7 @@ def block_main(args):
         cpu = {"value": round(B * iters / el, 2), "unit": "samples/s", "cores": threads, "kind": "port",
                "sample": f"oracle fp32 torch-CPU FFC_BN_ACT fwd (op-for-op reference path), B={B}, {iters} "
                          f"iterations in {el:.1f}s, {args.bn_mode}-mode BN"}
-    print(json.dumps({
-        "metric": "FFC_BN_ACT(32->32, k3, 0.5/0.5, BN, ReLU) fwd samples/sec @ B=16 32x32 (BASELINE configs[0])",
-        "value": round(value, 1), "unit": "samples/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(elapsed * 1e3 / args.steps, 4), "ms_per_step_median": round(med, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic: x ~ N(0,1); weights per fgan64_complete.py:22-31 weights_init",
-        "config": {"workload": "FFC_BN_ACT(32,32,3,0.5,0.5,stride=1,padding=1,BatchNorm2d,ReLU) forward 32x32",
-                   "global_batch": B, "per_gpu_batch": B, "bn_mode": args.bn_mode, "hipgraph": use_graph,
-                   "parallelism": "dp1"},
-        "roofline": roof, "cpu_baseline": cpu, "parity": parity, "kernels": kernels}))
+    return {"roofline": roof, "cpu_baseline": cpu, "parity": parity, "kernels": kernels}
 
 
 GLOBAL_BATCH = {"gen64": 256, "fgan128": 512, "fgan128sn": 1024,   # BASELINE.json configs[1..4]
@@ -686,6 +754,8 @@ def dry_run(args, world, rank):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     world, rank, local = ranks_or_launch(args)
     if args.dry_run:
         return dry_run(args, world, rank)
@@ -769,108 +839,113 @@ def main():
 
     for _ in range(max(1, args.warmup)):
         run()
-    elapsed, med = time_steps(run, args.steps, world)
+    elapsed, med, last = time_steps(run, args.steps, world)
     value = global_batch * args.steps / elapsed
     ms_per_step = elapsed * 1e3 / args.steps
+    if args.dump_outputs:
+        # the captured graph's static output after the last timed replay, or the last eager step's
+        dump_outputs(args.dump_outputs, {"images": graph.ffc_output if use_graph else last}, rank, world)
 
-    weak = None
-    if world > 1 and args.scaling == "strong":
-        # beside the strong split: every GPU runs the configuration's whole batch (SURVEY.md §8e "report
-        # weak scaling alongside"), z from the same seed, SyncBN over the N x larger global batch
-        per = WEAK_BATCH[args.workload]
-        zw = torch.randn((per * world, 128) if fgan else (per * world, args.nz, 1, 1),
-                         generator=torch.Generator(device="cpu").manual_seed(100))[rank * per:(rank + 1) * per].to(dev)
+    weak = roof = fft_roof = cpu = parity = kernels = None
+    if args.full:
+        if world > 1 and args.scaling == "strong":
+            # beside the strong split: every GPU runs the configuration's whole batch (SURVEY.md §8e "report
+            # weak scaling alongside"), z from the same seed, SyncBN over the N x larger global batch
+            per = WEAK_BATCH[args.workload]
+            zw = torch.randn((per * world, 128) if fgan else (per * world, args.nz, 1, 1),
+                             generator=torch.Generator(device="cpu").manual_seed(100))
+            zw = zw[rank * per:(rank + 1) * per].to(dev)
 
-        def step_w():
+            def step_w():
+                with torch.no_grad():
+                    return G.forward_float(zw) if fgan else G(zw)
+            for _ in range(max(1, args.warmup)):
+                step_w()
+            gw = capture_step(step_w, warmup=1) if use_graph else None
+            run_w = gw.replay if gw is not None else step_w
+            for _ in range(max(1, args.warmup)):
+                run_w()
+            el_w, med_w, _ = time_steps(run_w, args.steps, world)
+            weak = {"value": round(per * world * args.steps / el_w, 1), "unit": "images/s", "per_gpu_batch": per,
+                    "global_batch": per * world, "ms_per_step": round(el_w * 1e3 / args.steps, 4),
+                    "ms_per_step_median": round(med_w, 4), "hipgraph": gw is not None}
+            del gw
+
+        # ---- live per-kernel roofline: one instrumented eager pass (HIP events on the launch stream)
+        summ, out = profile_pass(step, args.profile_steps)
+        kernels = {k: {"launches_per_step": v["launches"] / max(1, args.profile_steps),
+                       "ms_per_step": v["ms"] / max(1, args.profile_steps),
+                       "avg_us": 1e3 * v["ms"] / v["launches"]} for k, v in summ.items()}
+        dom = max(summ, key=lambda k: summ[k]["ms"])
+        d = summ[dom]
+        if d["flops"] > 0:
+            achieved = d["flops"] / (d["ms"] * 1e-3) / 1e12
+            roof = mfma_roof(dom, achieved)
+        else:
+            achieved = d["bytes"] / (d["ms"] * 1e-3) / 1e9
+            roof = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
+                    "frac": round(achieved / PEAK_HBM_GBS, 4)}
+        tr = pmc_traffic(dom, args.workload)
+        roof["traffic"] = tr["bytes_per_launch"] if tr else None
+        if tr:
+            roof["traffic_source"] = tr["source"]
+        fu = {k: summ[k] for k in ("fu_pass0", "fu_pass1", "fu2d_r2c", "fu2d_c2r") if k in summ}
+        fft_roof = None
+        if fu:
+            b = sum(v["bytes"] for v in fu.values())
+            ms = sum(v["ms"] for v in fu.values())
+            mv = sum(v["moved"] for v in fu.values())
+            fft_roof = {"kernel": "+".join(fu), "bound": "hbm", "achieved": round(b / (ms * 1e-3) / 1e9, 1),
+                        "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(b / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                        "basis": "SURVEY.md §8d algorithmic bytes per launch (fused train FU 12*N_r, R2C 4*N_r + "
+                                 "8*N_c, C2R 8*N_c + 4*N_r; no spill counted), each capped at the bytes the launch "
+                                 "moves (the upsample-folded R2C reads t and writes T, 1/4 of the formula)",
+                        "algorithmic_bytes_per_step": b / max(1, args.profile_steps),
+                        "moved_bytes_per_step": mv / max(1, args.profile_steps),
+                        "moved_frac": round(mv / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
+                        "ms_per_step": round(ms / max(1, args.profile_steps), 4),
+                        "per_stage": {k: {"us_per_launch": round(1e3 * v["ms"] / v["launches"], 2),
+                                          "frac": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
+                                      for k, v in fu.items()}}
+
+        # ---- CPU baseline + parity (rank 0, N=1 only); N > 1: the gathered sharded output (SyncBN)
+        cpu = None
+        parity = None
+        # the timed artifact: the captured graph's static output after the timed replays (train-mode
+        # BN: every replay computes the same output from the batch's own statistics)
+        timed_out = getattr(graph, "ffc_output", None) if use_graph else None
+        if world > 1 and not fgan and args.bn_mode == "train" and not args.no_cpu_baseline:
+            parity = sharded_parity(args, step, cpu_state, z_glob, global_batch, rank, timed_out)
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and fgan:
+            cpu, parity = fgan_cpu_baseline(args, G, z_cpu, sn)
+        elif rank == 0 and world == 1 and not args.no_cpu_baseline:
+            from oracle.ffc_oracle import ffc_generator, normwise_err
+            threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or min(16, os.cpu_count() or 1)
+            torch.set_num_threads(threads)
+            sd = {k: v.clone() for k, v in cpu_state.items()}
+            training = args.bn_mode == "train"
+            if not training:  # eval: use the GPU model's current running stats
+                sd = {k: v.detach().cpu().clone() for k, v in G.state_dict().items()}
             with torch.no_grad():
-                return G.forward_float(zw) if fgan else G(zw)
-        for _ in range(max(1, args.warmup)):
-            step_w()
-        gw = capture_step(step_w, warmup=1) if use_graph else None
-        run_w = gw.replay if gw is not None else step_w
-        for _ in range(max(1, args.warmup)):
-            run_w()
-        el_w, med_w = time_steps(run_w, args.steps, world)
-        weak = {"value": round(per * world * args.steps / el_w, 1), "unit": "images/s", "per_gpu_batch": per,
-                "global_batch": per * world, "ms_per_step": round(el_w * 1e3 / args.steps, 4),
-                "ms_per_step_median": round(med_w, 4), "hipgraph": gw is not None}
-        del gw
-
-    # ---- live per-kernel roofline: one instrumented eager pass (HIP events on the launch stream)
-    summ, out = profile_pass(step, args.profile_steps)
-    kernels = {k: {"launches_per_step": v["launches"] / max(1, args.profile_steps),
-                   "ms_per_step": v["ms"] / max(1, args.profile_steps),
-                   "avg_us": 1e3 * v["ms"] / v["launches"]} for k, v in summ.items()}
-    dom = max(summ, key=lambda k: summ[k]["ms"])
-    d = summ[dom]
-    if d["flops"] > 0:
-        achieved = d["flops"] / (d["ms"] * 1e-3) / 1e12
-        roof = mfma_roof(dom, achieved)
-    else:
-        achieved = d["bytes"] / (d["ms"] * 1e-3) / 1e9
-        roof = {"kernel": dom, "bound": "hbm", "achieved": round(achieved, 1), "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                "frac": round(achieved / PEAK_HBM_GBS, 4)}
-    tr = pmc_traffic(dom, args.workload)
-    roof["traffic"] = tr["bytes_per_launch"] if tr else None
-    if tr:
-        roof["traffic_source"] = tr["source"]
-    fu = {k: summ[k] for k in ("fu_pass0", "fu_pass1", "fu2d_r2c", "fu2d_c2r") if k in summ}
-    fft_roof = None
-    if fu:
-        b = sum(v["bytes"] for v in fu.values())
-        ms = sum(v["ms"] for v in fu.values())
-        mv = sum(v["moved"] for v in fu.values())
-        fft_roof = {"kernel": "+".join(fu), "bound": "hbm", "achieved": round(b / (ms * 1e-3) / 1e9, 1),
-                    "peak": PEAK_HBM_GBS, "unit": "GB/s", "frac": round(b / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                    "basis": "SURVEY.md §8d algorithmic bytes per launch (fused train FU 12*N_r, R2C 4*N_r + "
-                             "8*N_c, C2R 8*N_c + 4*N_r; no spill counted), each capped at the bytes the launch "
-                             "moves (the upsample-folded R2C reads t and writes T, 1/4 of the formula)",
-                    "algorithmic_bytes_per_step": b / max(1, args.profile_steps),
-                    "moved_bytes_per_step": mv / max(1, args.profile_steps),
-                    "moved_frac": round(mv / (ms * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
-                    "ms_per_step": round(ms / max(1, args.profile_steps), 4),
-                    "per_stage": {k: {"us_per_launch": round(1e3 * v["ms"] / v["launches"], 2),
-                                      "frac": round(v["bytes"] / (v["ms"] * 1e-3) / 1e9 / PEAK_HBM_GBS, 4)}
-                                  for k, v in fu.items()}}
-
-    # ---- CPU baseline + parity (rank 0, N=1 only); N > 1: the gathered sharded output (SyncBN)
-    cpu = None
-    parity = None
-    # the timed artifact: the captured graph's static output after the timed replays (train-mode
-    # BN: every replay computes the same output from the batch's own statistics)
-    timed_out = getattr(graph, "ffc_output", None) if use_graph else None
-    if world > 1 and not fgan and args.bn_mode == "train" and not args.no_cpu_baseline:
-        parity = sharded_parity(args, step, cpu_state, z_glob, global_batch, rank, timed_out)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and fgan:
-        cpu, parity = fgan_cpu_baseline(args, G, z_cpu, sn)
-    elif rank == 0 and world == 1 and not args.no_cpu_baseline:
-        from oracle.ffc_oracle import ffc_generator, normwise_err
-        threads = int(os.environ.get("OMP_NUM_THREADS", "0")) or min(16, os.cpu_count() or 1)
-        torch.set_num_threads(threads)
-        sd = {k: v.clone() for k, v in cpu_state.items()}
-        training = args.bn_mode == "train"
-        if not training:  # eval: use the GPU model's current running stats
-            sd = {k: v.detach().cpu().clone() for k, v in G.state_dict().items()}
-        with torch.no_grad():
-            ref = ffc_generator(z_cpu, sd, args.nz, args.nc, args.ngf, training, fft="torch")
-            iters, t0 = 1, time.perf_counter()
-            while time.perf_counter() - t0 < args.cpu_seconds:
-                ffc_generator(z_cpu, sd, args.nz, args.nc, args.ngf, training, fft="torch")
-                iters += 1
-            cpu_el = time.perf_counter() - t0
-        with torch.no_grad():
-            if timed_out is not None and training:
-                torch.cuda.synchronize()
-                gpu_out, source = timed_out.cpu(), "captured hipGraph's output after the timed replays"
-            else:   # eval mode: the profile pass moved nothing, any forward is the timed one
-                gpu_out, source = step().cpu(), "eager forward" if timed_out is None else \
-                    "eager forward (eval-mode BN: the same kernels and running statistics as the graph)"
-        parity = {"normwise_err_vs_cpu_ref": normwise_err(gpu_out, ref),
-                  "max_abs_diff": float((gpu_out - ref).abs().max()), "tolerance": 1e-4, "checked": source}
-        cpu = {"value": round(args.batch * (iters - 1) / cpu_el, 2), "unit": "images/s", "cores": threads,
-               "kind": "port",
-               "sample": f"oracle fp32 torch-CPU FFCGenerator fwd (op-for-op reference path), B={args.batch}, "
-                         f"{iters - 1} timed iterations in {cpu_el:.1f}s, {args.bn_mode}-mode BN"}
+                ref = ffc_generator(z_cpu, sd, args.nz, args.nc, args.ngf, training, fft="torch")
+                iters, t0 = 1, time.perf_counter()
+                while time.perf_counter() - t0 < args.cpu_seconds:
+                    ffc_generator(z_cpu, sd, args.nz, args.nc, args.ngf, training, fft="torch")
+                    iters += 1
+                cpu_el = time.perf_counter() - t0
+            with torch.no_grad():
+                if timed_out is not None and training:
+                    torch.cuda.synchronize()
+                    gpu_out, source = timed_out.cpu(), "captured hipGraph's output after the timed replays"
+                else:   # eval mode: the profile pass moved nothing, any forward is the timed one
+                    gpu_out, source = step().cpu(), "eager forward" if timed_out is None else \
+                        "eager forward (eval-mode BN: the same kernels and running statistics as the graph)"
+            parity = {"normwise_err_vs_cpu_ref": normwise_err(gpu_out, ref),
+                      "max_abs_diff": float((gpu_out - ref).abs().max()), "tolerance": 1e-4, "checked": source}
+            cpu = {"value": round(args.batch * (iters - 1) / cpu_el, 2), "unit": "images/s", "cores": threads,
+                   "kind": "port",
+                   "sample": f"oracle fp32 torch-CPU FFCGenerator fwd (op-for-op reference path), B={args.batch}, "
+                             f"{iters - 1} timed iterations in {cpu_el:.1f}s, {args.bn_mode}-mode BN"}
 
     if rank == 0:
         metric = METRIC if not fgan else (
@@ -891,9 +966,11 @@ def main():
                        "hipgraph": use_graph, "parallelism": f"dp{world}" + ("+syncbn" if world > 1 and
                                                                           args.bn_mode == "train" else "")
                        + ("+syncbn-rehearsal(1-rank RCCL group)" if world == 1 and args.syncbn_rehearsal else "")},
-            "roofline": roof, "fft_roofline": fft_roof, "cpu_baseline": cpu, "parity": parity,
-            "kernels": kernels,
+            "full": args.full,
         }
+        if args.full:
+            line.update({"roofline": roof, "fft_roofline": fft_roof, "cpu_baseline": cpu, "parity": parity,
+                         "kernels": kernels})
         if weak is not None:
             line["weak_scaling"] = weak
         print(json.dumps(line))

@@ -76,6 +76,35 @@ def test_launcher_world_mismatch_fails():
     assert res.returncode == 3 and "WORLD_SIZE=2" in res.stderr
 
 
+def test_dump_outputs_files_and_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 <name>.npy per output; an output over its share of the byte budget is
+    cut to the same seeded batch rows in every call, and the files together stay within the budget"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 4 * 2 * 40)       # 40 floats per output
+    small = torch.arange(24, dtype=torch.float64).reshape(4, 6)
+    big = torch.arange(16 * 8, dtype=torch.float32).reshape(16, 2, 4)  # 128 floats: 5 rows of 8 fit
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "big": big})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float32 and a.dtype == np.float32
+    assert np.array_equal(s, small.numpy().astype(np.float32))
+    assert a.shape == (5, 2, 4) and np.array_equal(a, b)
+    rows = (a[:, 0, 0] / 8).astype(int)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(a, big.numpy()[rows])
+    assert a.nbytes + s.nbytes <= bench.DUMP_BUDGET_BYTES
+    bench.dump_outputs(str(tmp_path / "r"), {"small": small}, rank=1, world=2)
+    assert os.path.exists(tmp_path / "r" / "small_rank1.npy")
+
+
+def test_steps_must_be_positive():
+    res = _bench("--steps", "0", "--dry-run")
+    assert res.returncode != 0 and "--steps" in res.stderr
+
+
 def test_spawn_ranks_env_and_failure(tmp_path):
     """every rank sees its own RANK / LOCAL_RANK and the shared WORLD_SIZE / MASTER_*; one failing
     rank fails the job and the others are stopped"""

@@ -13,7 +13,7 @@ for round in 1 2; do
     if [ "$name" != "$v" ]; then envs=${v#*+}; fi
     if [ "$name" = cur ]; then lib=""; else lib="fastfourierconvolution_amd/libffc_amd_$name.so"; fi
     tag=$(echo "$v" | tr '+=/' '___')
-    env FFC_LIB_PATH=$lib $envs timeout -k 10 300 python bench.py --steps ${AB_STEPS:-50} --warmup 5 --no-cpu-baseline ${AB_ARGS:-} \
+    env FFC_LIB_PATH=$lib $envs timeout -k 10 300 python bench.py --full --steps ${AB_STEPS:-50} --warmup 5 --no-cpu-baseline ${AB_ARGS:-} \
       > gpurun_out/${AB_PREFIX:-}ab_$tag.log 2>&1
     rc=$?
     if [ $rc -ne 0 ]; then echo "variant $v rc=$rc"; tail -5 gpurun_out/${AB_PREFIX:-}ab_$tag.log; exit $rc; fi

@@ -16,7 +16,7 @@ fi
 for gb in ${BATCHES:-64 512}; do
   for v in ${VARIANTS:-11 01 10 00}; do
     d=${v:0:1}; sp=${v:1:1}
-    FFC_DEFER_HEAD=$d FFC_FU2D_SPILL=$sp timeout -k 10 240 python bench.py --workload fgan128 --global-batch $gb \
+    FFC_DEFER_HEAD=$d FFC_FU2D_SPILL=$sp timeout -k 10 240 python bench.py --full --workload fgan128 --global-batch $gb \
       --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline > gpurun_out/${tag}_fgan_${gb}_$v.log 2>&1
     rc=$?
     echo "fgan128 B=$gb defer=$d spill=$sp rc=$rc"

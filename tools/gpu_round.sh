@@ -20,14 +20,14 @@ if [ -z "${SKIP_TESTS:-}" ]; then
   run tests 900 python -u -m pytest tests -m gpu -x -q --timeout 180 --timeout-method thread
   tail -1 $o/tests.log
 fi
-run bench_gen64 300 python bench.py --cpu-seconds 10
-run bench_fgan128 300 python bench.py --workload fgan128 --steps 50 --warmup 3 --cpu-seconds 10
-run bench_fgan128sn 300 python bench.py --workload fgan128sn --steps 30 --warmup 3 --cpu-seconds 10
-run bench_gan64train 300 python bench.py --workload gan64train --steps 50 --warmup 3 --cpu-seconds 10
-run bench_block 300 python bench.py --workload block --cpu-seconds 10
+run bench_gen64 300 python bench.py --full --cpu-seconds 10
+run bench_fgan128 300 python bench.py --full --workload fgan128 --steps 50 --warmup 3 --cpu-seconds 10
+run bench_fgan128sn 300 python bench.py --full --workload fgan128sn --steps 30 --warmup 3 --cpu-seconds 10
+run bench_gan64train 300 python bench.py --full --workload gan64train --steps 50 --warmup 3 --cpu-seconds 10
+run bench_block 300 python bench.py --full --workload block --cpu-seconds 10
 run rocprof_gen64 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_gen64 -o run -- python3 bench.py --steps 100 --warmup 5 --no-cpu-baseline
 run rocprof_fgan128 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_fgan128 -o run -- python3 bench.py --workload fgan128 --steps 10 --warmup 3 --no-cpu-baseline
-run bench_fgan128train 300 python bench.py --workload fgan128train --steps 20 --warmup 3 --cpu-seconds 10
+run bench_fgan128train 300 python bench.py --full --workload fgan128train --steps 20 --warmup 3 --cpu-seconds 10
 for b in 128 64 32; do
   run bench_gen64_shard_$b 300 python bench.py --batch $b --steps 200 --warmup 5 --no-cpu-baseline --scaling weak
 done

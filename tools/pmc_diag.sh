@@ -16,7 +16,7 @@ for W in "$@"; do
               "b:SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_BUSY_CYCLES SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_ANY SQ_INST_LEVEL_VMEM"; do
     name=${pass%%:*}; ctrs=${pass#*:}
     timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $d/$name -o run -- \
-        python3 bench.py --workload $W $steps --no-cpu-baseline --no-graph --profile-steps 1 > $d/$name.log 2>&1
+        python3 bench.py --full --workload $W $steps --no-cpu-baseline --no-graph --profile-steps 1 > $d/$name.log 2>&1
     rc=$?
     echo "$W pass $name rc=$rc"
     if [ $rc -ne 0 ]; then tail -20 $d/$name.log; exit $rc; fi

@@ -16,7 +16,7 @@ for W in "$@"; do
   for pass in "mfma:SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES" "fetch:FETCH_SIZE" "write:WRITE_SIZE"; do
     name=${pass%%:*}; ctrs=${pass#*:}
     timeout -s KILL 240 rocprofv3 --kernel-trace --pmc $ctrs --output-format csv -d $d/$name -o run -- \
-        python3 bench.py --workload $W $steps --no-cpu-baseline --no-graph --profile-steps 1 > $d/$name.log 2>&1
+        python3 bench.py --full --workload $W $steps --no-cpu-baseline --no-graph --profile-steps 1 > $d/$name.log 2>&1
     rc=$?
     echo "$W pass $name rc=$rc"
     if [ $rc -ne 0 ]; then tail -20 $d/$name.log; exit $rc; fi

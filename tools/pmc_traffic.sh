@@ -13,7 +13,7 @@ mkdir -p gpurun_out/pmc_traffic_$WORKLOAD profiles/$ROUND
 export TMPDIR=/tmp
 for c in FETCH_SIZE WRITE_SIZE; do
   timeout -k 10 300 rocprofv3 --kernel-trace --pmc $c --output-format csv -d gpurun_out/pmc_traffic_$WORKLOAD/$c -o run -- \
-      python bench.py --workload $WORKLOAD --steps 3 --warmup 2 --no-cpu-baseline --no-graph --profile-steps 1 \
+      python bench.py --full --workload $WORKLOAD --steps 3 --warmup 2 --no-cpu-baseline --no-graph --profile-steps 1 \
       > gpurun_out/pmc_traffic_$WORKLOAD/$c.log 2>&1
   rc=$?
   echo "pass $c rc=$rc"

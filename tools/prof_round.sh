@@ -14,10 +14,10 @@ run() {  # name timeout cmd...
 }
 run smoke 120 python -c "import __graft_entry__ as g; g.smoke()"
 tail -1 gpurun_out/smoke.log
-run bench_gen64 300 python bench.py --steps 50 --warmup 5 --cpu-seconds 10
-run bench_fgan128 300 python bench.py --workload fgan128 --steps 20 --warmup 3 --cpu-seconds 10
-run bench_fgan128sn 300 python bench.py --workload fgan128sn --steps 20 --warmup 3 --cpu-seconds 10
-run bench_gan64train 300 python bench.py --workload gan64train --steps 20 --warmup 3 --cpu-seconds 10
+run bench_gen64 300 python bench.py --full --steps 50 --warmup 5 --cpu-seconds 10
+run bench_fgan128 300 python bench.py --full --workload fgan128 --steps 20 --warmup 3 --cpu-seconds 10
+run bench_fgan128sn 300 python bench.py --full --workload fgan128sn --steps 20 --warmup 3 --cpu-seconds 10
+run bench_gan64train 300 python bench.py --full --workload gan64train --steps 20 --warmup 3 --cpu-seconds 10
 run rocprof_gen64 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_gen64 -o run -- python3 bench.py --steps 20 --warmup 3 --no-cpu-baseline
 find gpurun_out/prof_gen64 -name "*stats*"
 ROUND=${ROUND:-pmc} bash tools/pmc_traffic.sh || exit $?
