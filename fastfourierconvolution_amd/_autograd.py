@@ -661,3 +661,150 @@ def spectral_v(st, x):
     (t,) = conv_layer(B, [(c, 0, 0.0)], [(0, 0, _plan.Seg("pw", Cin, H, W), st.conv1)], [x])
     s = bn_act(st.bn1, t, (1, 0.0))
     return fourier_unit(st.fu, s, residual=True)
+
+
+# --------------------------------------------------------------------------- class-conditional fgan128
+def _labels(labels, B, what):
+    """class labels as the kernels read them: an int64 device tensor (B,) (never read on the host)"""
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError(f"{what}: labels must be a tensor, got {type(labels).__name__}")
+    if not labels.is_cuda:
+        raise FFCError(f"{what}: labels must be on a ROCm/HIP device (there is no CPU fallback)")
+    if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != B:
+        raise RuntimeError(f"{what}: labels must be int64 of shape ({B},), got {labels.dtype} {tuple(labels.shape)}")
+    return labels.contiguous()
+
+
+STEM_CH = 256   # channels of each stem branch (ngf * 4, fgan128_cond_complete.py:74-85)
+
+
+def cond_stem_impl(z, labels, embed, w_in, b_in, w_label, b_label, gamma_in, beta_in, gamma_label, beta_label,
+                   rmean_in, rvar_in, rmean_label, rvar_label, use_batch, eps):
+    """ffc::cond_stem: FCondGenerator's stem (fgan128_cond_complete.py:91-101),
+    cat([GELU(BN(ConvT(z))), GELU(BN(ConvT(label_embed[labels])))], 1) -> [y, pre, scale, shift, stats].
+    pre: the (B, 512, 4, 4) ConvTranspose2d outputs of both branches (ffc_cond_stem_forward); scale /
+    shift (512): the two BatchNorms folded; stats: the fp64 batch moments [512][3] with batch
+    statistics (the input of ffc::bn_update_running and of the backward), else the running (mean, var)
+    [2][512]"""
+    z = rt.require(z, "z")
+    B, K = z.shape
+    labels = _labels(labels, B, "cond_stem")
+    NC = embed.shape[0]
+    C = STEM_CH
+    if tuple(embed.shape) != (NC, NC) or tuple(w_in.shape) != (K, C, 4, 4) or tuple(w_label.shape) != (NC, C, 4, 4):
+        raise RuntimeError(f"cond_stem: label_embed {tuple(embed.shape)}, input_conv {tuple(w_in.shape)}, "
+                           f"label_conv {tuple(w_label.shape)} do not form the stem of z {tuple(z.shape)}")
+    if use_batch and rt._sync_group() is not None:
+        raise NotImplementedError("the conditional stem's BatchNorms have no SyncBN path (sharded conditional "
+                                  "training is not supported)")
+    ts = [rt.require(t.detach(), "cond_stem parameter") for t in (embed, w_in, b_in, w_label, b_label, gamma_in,
+                                                                   beta_in, gamma_label, beta_label)]
+    embed, w_in, b_in, w_label, b_label, gamma_in, beta_in, gamma_label, beta_label = ts
+    L = rt.lib()
+    dev, stream = z.device, _stream(z)
+    pre = torch.empty((B, 2 * C, 4, 4), device=dev, dtype=torch.float32)
+    scale = torch.empty(2 * C, device=dev, dtype=torch.float32)
+    shift = torch.empty(2 * C, device=dev, dtype=torch.float32)
+    slab = None
+    if use_batch:
+        rows = L.ffc_cond_stem_slab_rows(B)
+        if L.ffc_bn_reduce_ws_doubles(rows, C):
+            raise NotImplementedError(f"cond_stem: batch {B} is beyond the single-launch BN merge")
+        slab = torch.empty((2, rows, C, 4), device=dev, dtype=torch.float32)
+    with rt.observe("cond_stem", flops=2.0 * B * (K + NC) * C * 16):
+        check(L.ffc_cond_stem_forward(ptr(z), ptr(labels), ptr(embed), ptr(w_in), ptr(b_in), ptr(w_label),
+                                      ptr(b_label), B, K, NC, ptr(pre), ptr(slab), stream), "ffc_cond_stem_forward")
+    if use_batch:
+        from ._lib import BnRfItem
+        stats = torch.empty((2 * C, 3), device=dev, dtype=torch.float64)
+        arr = (BnRfItem * 2)()
+        for k, (g, b) in enumerate(((gamma_in, beta_in), (gamma_label, beta_label))):
+            arr[k] = BnRfItem(ptr(slab[k]), rows, C, ptr(stats[k * C:]), ptr(g), ptr(b), None, None, None, 0, 0.1,
+                              float(eps), 1.0, ptr(scale[k * C:]), ptr(shift[k * C:]))
+        with rt.observe("bn_stats"):
+            check(L.ffc_bn_reduce_finalize_batch(arr, 2, stream), "ffc_bn_reduce_finalize_batch")
+    else:
+        stats = torch.stack((torch.cat((rmean_in.detach(), rmean_label.detach())),
+                             torch.cat((rvar_in.detach(), rvar_label.detach())))).float().contiguous()
+        for k, (g, b) in enumerate(((gamma_in, beta_in), (gamma_label, beta_label))):
+            check(L.ffc_bn_finalize(None, C, ptr(g), ptr(b), ptr(stats[0, k * C:]), ptr(stats[1, k * C:]), None, 0, 0,
+                                    0.1, float(eps), 1.0, ptr(scale[k * C:]), ptr(shift[k * C:]), stream),
+                  "ffc_bn_finalize")
+    y = torch.empty_like(pre)
+    from ._lib import BnApplyItem
+    item = (BnApplyItem * 1)()
+    item[0] = BnApplyItem(ptr(pre), ptr(y), B, 2 * C, 16, ptr(scale), ptr(shift), 5, 0.0, None, None, None)
+    with rt.observe("bn_act", bytes=8.0 * pre.numel()):
+        check(L.ffc_bn_act_apply_batch(item, 1, stream), "ffc_bn_act_apply_batch")
+    return [y, pre, scale, shift, stats]
+
+
+def cond_stem_backward_impl(dpre, z, labels, embed, w_in, w_label, needs):
+    """ffc::cond_stem_backward: needs = [dz, d label_embed, dw_in, db_in, dw_label, db_label] -> those
+    gradients (empty tensors where not needed); deterministic (ffc_cond_stem_backward)"""
+    dpre = rt.require(dpre, "dpre")
+    z = z.contiguous()
+    B, K = z.shape
+    NC = embed.shape[0]
+    dev = z.device
+    embed, w_in, w_label = embed.contiguous(), w_in.contiguous(), w_label.contiguous()
+    shapes = [(B, K), (NC, NC), tuple(w_in.shape), (STEM_CH,), tuple(w_label.shape), (STEM_CH,)]
+    outs = [torch.empty(s if n else (0,), device=dev, dtype=torch.float32) for s, n in zip(shapes, needs)]
+    p = [ptr(t) if n else None for t, n in zip(outs, needs)]
+    ws = torch.empty(B * NC, device=dev, dtype=torch.float32) if needs[1] else None
+    with rt.observe("cond_stem_bwd", flops=2.0 * B * (K + NC) * STEM_CH * 16):
+        check(rt.lib().ffc_cond_stem_backward(ptr(dpre), ptr(z), ptr(labels.contiguous()), ptr(embed), ptr(w_in),
+                                              ptr(w_label), B, K, NC, p[2], p[3], p[4], p[5], p[0], p[1], ptr(ws),
+                                              _stream(z)), "ffc_cond_stem_backward")
+    return outs
+
+
+def embed_rows_impl(weight, labels):
+    """ffc::embed_rows: nn.Embedding lookup weight[labels] -> (B, D) (ffc_embed_gather_rows)"""
+    weight = rt.require(weight, "label_embed.weight")
+    NC, D = weight.shape
+    B = labels.shape[0]
+    labels = _labels(labels, B, "embed_rows")
+    out = torch.empty((B, D), device=weight.device, dtype=torch.float32)
+    with rt.observe("embed_gather", bytes=8.0 * out.numel()):
+        check(rt.lib().ffc_embed_gather_rows(ptr(weight), ptr(labels), B, NC, D, ptr(out), _stream(weight)),
+              "ffc_embed_gather_rows")
+    return out
+
+
+def embed_rows_backward_impl(grad, labels, num_classes):
+    """ffc::embed_rows_backward: the per-class sums of the rows of grad (B, D), in sample order ->
+    (num_classes, D); zeros for absent classes (ffc_embed_scatter_rows)"""
+    grad = rt.require(grad, "grad")
+    B, D = grad.shape
+    out = torch.empty((num_classes, D), device=grad.device, dtype=torch.float32)
+    with rt.observe("embed_scatter", bytes=4.0 * grad.numel() + 4.0 * out.numel()):
+        check(rt.lib().ffc_embed_scatter_rows(ptr(grad), ptr(labels.contiguous()), B, num_classes, D, ptr(out),
+                                              _stream(grad)), "ffc_embed_scatter_rows")
+    return out
+
+
+def cond_stem(mod, z, labels):
+    """FCondGenerator's stem over its modules (input_conv, label_conv, label_embed) on ffc::cond_stem,
+    then nn.BatchNorm2d's running-statistics updates in training mode"""
+    conv_i, bn_i, act_i = mod.input_conv
+    conv_l, bn_l, act_l = mod.label_conv
+    for bn in (bn_i, bn_l):
+        if bn.weight is None or bn.running_mean is None:
+            raise NotImplementedError("cond_stem: affine BatchNorm2d with running statistics only")
+    if rt.act_code(act_i) != (5, 0.0) or rt.act_code(act_l) != (5, 0.0):
+        raise NotImplementedError("cond_stem: the stem's activation is GELU")
+    modes = {rt.bn_mode(bn_i), rt.bn_mode(bn_l)}
+    if len(modes) != 1 or bn_i.eps != bn_l.eps:
+        raise NotImplementedError("cond_stem: both stem BatchNorms must be in the same mode, with the same eps")
+    use_batch, update = modes.pop()
+    y, _, _, _, stats = torch.ops.ffc.cond_stem(
+        z, labels, mod.label_embed.weight, conv_i.weight, conv_i.bias, conv_l.weight, conv_l.bias, bn_i.weight,
+        bn_i.bias, bn_l.weight, bn_l.bias, bn_i.running_mean, bn_i.running_var, bn_l.running_mean, bn_l.running_var,
+        use_batch, float(bn_i.eps))
+    if update:
+        for k, bn in enumerate((bn_i, bn_l)):
+            torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked,
+                                            stats[k * STEM_CH:(k + 1) * STEM_CH],
+                                            -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
+    return y

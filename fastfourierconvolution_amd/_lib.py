@@ -223,6 +223,14 @@ SIGNATURES = [
                                      c_void_p, c_int, c_float, c_void_p]),
     ("ffc_pool2", c_int, [c_void_p, c_longlong, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("ffc_up2", c_int, [c_void_p, c_longlong, c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("ffc_cond_stem_slab_rows", c_int, [c_int]),
+    ("ffc_cond_stem_forward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                      c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    ("ffc_cond_stem_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p]),
+    ("ffc_embed_gather_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_embed_scatter_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
 ]
 
 _lock = threading.Lock()

@@ -24,7 +24,7 @@ import torch.distributed as dist
 from . import _runtime as rt
 
 __all__ = ["shard_range", "shard_batch", "broadcast_module", "enable_sync_bn", "disable_sync_bn",
-           "merge_moments", "gather_batch"]
+           "merge_moments", "gather_batch", "refuse_conditional"]
 
 
 def shard_range(global_batch: int, rank: int, world: int) -> tuple[int, int]:
@@ -49,9 +49,22 @@ def shard_batch(x: torch.Tensor, rank: int | None = None, world: int | None = No
 
 def broadcast_module(module: torch.nn.Module, src: int = 0, group=None) -> None:
     """Replicate parameters and buffers (running stats, num_batches_tracked) from ``src``."""
+    refuse_conditional(module)
     with torch.no_grad():
         for t in list(module.parameters()) + list(module.buffers()):
             dist.broadcast(t.data, src, group=group)
+
+
+def refuse_conditional(module: torch.nn.Module) -> None:
+    """Sharding the class-conditional fgan128 models is not supported: the two BatchNorms of
+    FCondGenerator's stem take their batch statistics inside the fused stem and have no SyncBN route,
+    so a sharded run would normalise every rank's slice on its own.  Raises for such a module (or one
+    containing it); the stem itself raises too when it meets an active SyncBN group in train mode."""
+    from .models import FCondDiscriminator, FCondGenerator
+    for m in module.modules():
+        if isinstance(m, (FCondGenerator, FCondDiscriminator)):
+            raise NotImplementedError(f"{type(m).__name__}: multi-GPU sharding of the conditional fgan128 models is "
+                                      "not supported (the stem BatchNorms have no synchronised path)")
 
 
 def enable_sync_bn(group=None, even_world1: bool = False) -> None:

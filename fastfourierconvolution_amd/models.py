@@ -141,23 +141,19 @@ class FGenerator(FFCModel):
         self.mg = mg
         ngf = self.ngf
         self.noise_to_feature = nn.Sequential(nn.Linear(z_size, (self.mg * self.mg) * self.ngf * 8))
+        self._build_trunk(ngf, ratio_g)
+
+    def _build_trunk(self, ngf, ratio_g):
+        """conv2..conv6 (x2 FFC_BN_ACT + NoiseInjection pairs) and the conv7 head at width ngf and global
+        ratio ratio_g (fgan128_complete.py:457-488; fgan128_cond_complete.py:43-70 at ngf = 64, 0.25)"""
         T = dict(activation_layer=nn.GELU, norm_layer=nn.BatchNorm2d, upsampling=True, uses_noise=True,
                  uses_sn=True)
-        self.conv2 = FFC_BN_ACT(ngf * 8, ngf * 4, 4, 0.0, ratio_g, stride=2, padding=1, **T)
-        self.lcl_noise2 = NoiseInjection(int(ngf * 4 * (1 - ratio_g)))
-        self.glb_noise2 = NoiseInjection(int(ngf * 4 * ratio_g))
-        self.conv3 = FFC_BN_ACT(ngf * 4, ngf * 2, 4, ratio_g, ratio_g, stride=2, padding=1, **T)
-        self.lcl_noise3 = NoiseInjection(int(ngf * 2 * (1 - ratio_g)))
-        self.glb_noise3 = NoiseInjection(int(ngf * 2 * ratio_g))
-        self.conv4 = FFC_BN_ACT(ngf * 2, ngf, 4, ratio_g, ratio_g, stride=2, padding=1, **T)
-        self.lcl_noise4 = NoiseInjection(int(ngf * (1 - ratio_g)))
-        self.glb_noise4 = NoiseInjection(int(ngf * ratio_g))
-        self.conv5 = FFC_BN_ACT(ngf, ngf, 4, ratio_g, ratio_g, stride=2, padding=1, **T)
-        self.lcl_noise5 = NoiseInjection(int(ngf * (1 - ratio_g)))
-        self.glb_noise5 = NoiseInjection(int(ngf * ratio_g))
-        self.conv6 = FFC_BN_ACT(ngf, ngf, 4, ratio_g, ratio_g, stride=2, padding=1, **T)
-        self.lcl_noise6 = NoiseInjection(int(ngf * (1 - ratio_g)))
-        self.glb_noise6 = NoiseInjection(int(ngf * ratio_g))
+        plan = ((2, ngf * 8, ngf * 4, 0.0), (3, ngf * 4, ngf * 2, ratio_g), (4, ngf * 2, ngf, ratio_g),
+                (5, ngf, ngf, ratio_g), (6, ngf, ngf, ratio_g))
+        for n, cin, cout, rin in plan:
+            setattr(self, f"conv{n}", FFC_BN_ACT(cin, cout, 4, rin, ratio_g, stride=2, padding=1, **T))
+            setattr(self, f"lcl_noise{n}", NoiseInjection(int(cout * (1 - ratio_g))))
+            setattr(self, f"glb_noise{n}", NoiseInjection(int(cout * ratio_g)))
         self.conv7 = FFC_BN_ACT(ngf, 3, 3, ratio_g, 0.0, stride=1, padding=1, activation_layer=nn.Tanh,
                                 norm_layer=nn.Identity, upsampling=False, uses_noise=True, uses_sn=True)
 
@@ -172,10 +168,8 @@ class FGenerator(FFCModel):
             return ag.linear(lin, z).view(B, -1, self.mg, self.mg)
         return torch.ops.ffc.linear(z, lin.weight, lin.bias).view(B, -1, self.mg, self.mg)
 
-    def forward_float(self, z, noises=None):
-        """FGenerator.forward up to the float image (:491-515): the eval-mode uint8 quantization of
-        :516-521 is left out"""
-        fake = self._noise_to_feature(z)                                     # :491-494
+    def _trunk(self, fake, noises=None):
+        """conv2..conv7 + Resizer on the (B, C, 4, 4) stem output (:496-515); shared with FCondGenerator"""
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         for i, n in enumerate((2, 3, 4, 5, 6)):                              # :496-515
             conv = getattr(self, f"conv{n}")
@@ -189,6 +183,11 @@ class FGenerator(FFCModel):
             else:
                 fake = conv.forward_deferred(fake) if defer else conv(fake)
         return self.resizer(self.conv7(fake))
+
+    def forward_float(self, z, noises=None):
+        """FGenerator.forward up to the float image (:491-515): the eval-mode uint8 quantization of
+        :516-521 is left out"""
+        return self._trunk(self._noise_to_feature(z), noises)                # :491-494
 
     def forward(self, z, noises=None):
         fake = self.forward_float(z, noises)
@@ -238,3 +237,98 @@ class Discriminator(FFCModel):
 
 
 FGanDiscriminator = Discriminator
+
+
+class FCondGenerator(FGenerator):
+    """fgan128_cond_complete.py:33-133: the class-conditional fgan128 generator.  The stem is two
+    ConvTranspose2d(k4, s1, p0) + BatchNorm2d + GELU branches on 1x1 inputs -- z, and the
+    label_embed row of each sample's class -- concatenated on channels (:91-101), one fused launch
+    sequence (ffc::cond_stem); conv2..conv7 are FGenerator's trunk at ngf = 64, global ratio 0.25.
+    Constructor, attribute names and state_dict keys are the reference's.
+
+    ``forward(z, labels, noises=None)``: labels (B,) int64 on the GPU, read by the kernels (a captured
+    forward replays with new labels written into the same tensor); ``noises`` as FGenerator.  A label
+    outside [0, num_classes) reads no memory outside the table: that sample's stem values are NaN."""
+
+    def __init__(self, z_size, mg: int = 4, num_classes: int = 10):
+        FFCModel.__init__(self)
+        self.z_size = z_size
+        self.ngf = 64
+        ratio_g = 0.25
+        self.mg = mg
+        self.num_classes = num_classes
+        self._build_trunk(self.ngf, ratio_g)
+        self.label_conv = nn.Sequential(nn.ConvTranspose2d(num_classes, self.ngf * 4, 4, 1, 0),
+                                        nn.BatchNorm2d(self.ngf * 4), nn.GELU())
+        self.input_conv = nn.Sequential(nn.ConvTranspose2d(z_size, self.ngf * 4, 4, 1, 0),
+                                        nn.BatchNorm2d(self.ngf * 4), nn.GELU())
+        self.label_embed = nn.Embedding(num_classes, num_classes)
+
+    def _stem(self, z, labels):
+        z = rt.require(z, "z")
+        if z.dim() == 4 and tuple(z.shape[2:]) == (1, 1):
+            z = z.reshape(z.shape[0], -1)                                     # :97
+        if z.dim() != 2 or z.shape[1] != self.z_size:
+            raise RuntimeError(f"FCondGenerator: z must be (B, {self.z_size}), got {tuple(z.shape)}")
+        return ag.cond_stem(self, z, labels)
+
+    def forward_float(self, z, labels, noises=None):
+        """forward up to the float image (:91-125), without the eval-mode uint8 quantization of :127-132"""
+        return self._trunk(self._stem(z, labels), noises)
+
+    def forward(self, z, labels, noises=None):
+        fake = self.forward_float(z, labels, noises)
+        if self.training:
+            return fake
+        return torch.ops.ffc.quantize_u8(fake)   # :127-132
+
+
+class _ConvSlice:
+    """input channels [c0, c1) of a Conv2d seen by conv_layer as a conv of its own: the weight is a view
+    of the (spectral-normalised) weight, so its gradient flows back to the parameter; ``bias`` rides on
+    one slice only.  The slice is made contiguous here (a differentiable copy of a few KB): the conv
+    plans key their packed weights by the tensor object they are handed, and a strided view would be
+    copied anew, unregistered, inside the op -- a later copy at a recycled address could then meet a
+    stale pack"""
+
+    def __init__(self, weight, c0, c1, bias):
+        self.weight = weight[:, c0:c1].contiguous()
+        self.bias = bias
+        self.out_channels = weight.shape[0]
+
+
+class FCondDiscriminator(Discriminator):
+    """fgan128_cond_complete.py:136-180 (``Discriminator`` there): the label-conditioned critic.
+    label_embed (num_classes, 128*128) gives every class a 128x128 plane that conv1 reads as a fourth
+    input channel (:159-169).  The plane is gathered by ffc::embed_rows and conv1 runs as a two-segment
+    conv job -- image (3 channels) + plane (1 channel), each with its slice of conv1's weight -- so the
+    (B, 4, 128, 128) concatenation is never built.  state_dict keys: conv1..conv9, fc, label_embed."""
+
+    CONVS = ((4, 64, 3, 1),) + Discriminator.CONVS[1:]
+
+    def __init__(self, sn: bool = True, mg: int = 4, num_classes: int = 10):
+        super().__init__(sn=sn, mg=mg)
+        self.num_classes = num_classes
+        self.label_embed = nn.Embedding(num_classes, 128 * 128)
+
+    def forward(self, x, labels):
+        x = rt.require(x, "x")
+        side = 32 * self.mg
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, side, side) or side != 128:
+            raise RuntimeError(f"FCondDiscriminator: x must be (B, 3, 128, 128) with mg = 4, got {tuple(x.shape)}")
+        B = x.shape[0]
+        act, param = rt.act_code(self.act)
+        plane = torch.ops.ffc.embed_rows(self.label_embed.weight, labels).view(B, 1, side, side)   # :160-163
+        conv = self.conv1
+        rt.sn_refresh_train(conv)   # the slices below must see this call's W / sigma
+        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)],
+                             [(0, 0, _plan.Seg("conv", 3, side, side, k, s, p), _ConvSlice(conv.weight, 0, 3, conv.bias)),
+                              (0, 1, _plan.Seg("conv", 1, side, side, k, s, p), _ConvSlice(conv.weight, 3, 4, None))],
+                             [x, plane])                                                            # :167-169
+        for i in range(2, len(self.CONVS) + 1):
+            conv = getattr(self, f"conv{i}")
+            B, C, H, W = m.shape
+            sg = _plan.Seg("conv", C, H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+            (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)], [(0, 0, sg, conv)], [m])
+        return ag.linear(self.fc, m.reshape(m.shape[0], -1))   # :178

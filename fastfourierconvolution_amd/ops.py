@@ -339,6 +339,108 @@ def _noise_setup_shape(ctx, inputs, output):
 
 noise_inject.register_autograd(_noise_bwd, setup_context=_noise_setup_shape)
 
+# ---------------------------------------------------------------- ffc::cond_stem / ffc::embed_rows
+# class-conditional fgan128 (fgan128_cond_complete.py:33-180); labels: an int64 device tensor the
+# kernels read (no host read: a captured step replays with new labels in the same buffer)
+
+
+@torch.library.custom_op("ffc::cond_stem", mutates_args=())
+def cond_stem(z: Tensor, labels: Tensor, label_embed: Tensor, w_in: Tensor, b_in: Tensor, w_label: Tensor,
+              b_label: Tensor, gamma_in: Tensor, beta_in: Tensor, gamma_label: Tensor, beta_label: Tensor,
+              rmean_in: Tensor, rvar_in: Tensor, rmean_label: Tensor, rvar_label: Tensor, use_batch: bool,
+              eps: float) -> List[Tensor]:
+    """FCondGenerator's stem (:91-101) -> [y (B, 512, 4, 4), pre, scale, shift, stats]; functional (the
+    running statistics are updated by ffc::bn_update_running from stats)"""
+    return ag.cond_stem_impl(z, labels, label_embed, w_in, b_in, w_label, b_label, gamma_in, beta_in, gamma_label,
+                             beta_label, rmean_in, rvar_in, rmean_label, rvar_label, use_batch, eps)
+
+
+@cond_stem.register_fake
+def _(z, labels, label_embed, w_in, b_in, w_label, b_label, gamma_in, beta_in, gamma_label, beta_label, rmean_in,
+      rvar_in, rmean_label, rvar_label, use_batch, eps):
+    C = 2 * ag.STEM_CH
+    y = z.new_empty((z.shape[0], C, 4, 4))
+    stats = z.new_empty((C, 3), dtype=torch.float64) if use_batch else z.new_empty((2, C))
+    return [y, torch.empty_like(y), z.new_empty(C), z.new_empty(C), stats]
+
+
+@torch.library.custom_op("ffc::cond_stem_backward", mutates_args=())
+def cond_stem_backward(dpre: Tensor, z: Tensor, labels: Tensor, label_embed: Tensor, w_in: Tensor, w_label: Tensor,
+                       needs: List[bool]) -> List[Tensor]:
+    """-> [dz, d label_embed, dw_in, db_in, dw_label, db_label] (empty tensors where not needed)"""
+    return ag.cond_stem_backward_impl(dpre, z, labels, label_embed, w_in, w_label, needs)
+
+
+@cond_stem_backward.register_fake
+def _(dpre, z, labels, label_embed, w_in, w_label, needs):
+    shapes = [z.shape, label_embed.shape, w_in.shape, (ag.STEM_CH,), w_label.shape, (ag.STEM_CH,)]
+    return [z.new_empty(s if n else (0,)) for s, n in zip(shapes, needs)]
+
+
+def _cond_stem_setup(ctx, inputs, output):
+    z, labels, embed, w_in, b_in, w_label, b_label, gamma_in, beta_in, gamma_label, beta_label = inputs[:11]
+    _, pre, scale, shift, stats = output
+    ctx.mark_non_differentiable(pre, scale, shift, stats)
+    ctx.use_batch, ctx.eps = inputs[15], float(inputs[16])
+    ctx.needs = [bool(t.requires_grad) for t in (z, embed, w_in, b_in, w_label, b_label)]
+    ctx.needs_bn = [bool(t.requires_grad) for t in (gamma_in, beta_in, gamma_label, beta_label)]
+    ctx.save_for_backward(z, labels, embed, w_in, w_label, pre, scale, shift, stats,
+                          torch.cat((gamma_in.detach(), gamma_label.detach())))
+
+
+def _cond_stem_bwd(ctx, grads):
+    dy = grads[0]
+    if dy is None:
+        return (None,) * 17
+    z, labels, embed, w_in, w_label, pre, scale, shift, stats, gamma = ctx.saved_tensors
+    dpre, dgamma, dbeta = torch.ops.ffc.bn_act_backward(pre, dy, scale, shift, stats, gamma, ctx.use_batch, False,
+                                                        ctx.eps, 5, 0.0, True, True, True)
+    dz, dembed, dw_in, db_in, dw_label, db_label = torch.ops.ffc.cond_stem_backward(dpre, z, labels, embed, w_in,
+                                                                                    w_label, ctx.needs)
+    C = ag.STEM_CH
+    bn = (dgamma[:C], dbeta[:C], dgamma[C:], dbeta[C:])
+    n = ctx.needs
+    return (dz if n[0] else None, None, dembed if n[1] else None, dw_in if n[2] else None, db_in if n[3] else None,
+            dw_label if n[4] else None, db_label if n[5] else None) + \
+        tuple(g if need else None for g, need in zip(bn, ctx.needs_bn)) + (None,) * 6
+
+
+cond_stem.register_autograd(_cond_stem_bwd, setup_context=_cond_stem_setup)
+
+
+@torch.library.custom_op("ffc::embed_rows", mutates_args=())
+def embed_rows(weight: Tensor, labels: Tensor) -> Tensor:
+    """nn.Embedding lookup weight[labels] -> (B, D) (the critic's label plane, :159-163)"""
+    return ag.embed_rows_impl(weight, labels)
+
+
+@embed_rows.register_fake
+def _(weight, labels):
+    return weight.new_empty((labels.shape[0], weight.shape[1]))
+
+
+@torch.library.custom_op("ffc::embed_rows_backward", mutates_args=())
+def embed_rows_backward(grad: Tensor, labels: Tensor, num_classes: int) -> Tensor:
+    return ag.embed_rows_backward_impl(grad, labels, num_classes)
+
+
+@embed_rows_backward.register_fake
+def _(grad, labels, num_classes):
+    return grad.new_empty((num_classes, grad.shape[1]))
+
+
+def _embed_rows_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[1])
+    ctx.num_classes = inputs[0].shape[0]
+
+
+def _embed_rows_bwd(ctx, g):
+    (labels,) = ctx.saved_tensors
+    return torch.ops.ffc.embed_rows_backward(g, labels, ctx.num_classes), None
+
+
+embed_rows.register_autograd(_embed_rows_bwd, setup_context=_embed_rows_setup)
+
 # =========================================================================== inference ops
 
 

@@ -22,45 +22,57 @@ def hinge_loss_gen(fake):
     return -fake.mean()
 
 
-def generator_step(G, D, optim_G, optim_D, z, noises=None):
+def generator_step(G, D, optim_G, optim_D, z, noises=None, labels=None):
     """fgan128_complete.py:680-690: G trainable, D frozen; loss_G = hinge_loss_gen(D(G(z))), backward
     through D into G, optim_G.step().  ``noises``: explicit NoiseInjection noise (FGenerator.forward);
-    None draws it on the GPU as the reference does."""
+    None draws it on the GPU as the reference does.  ``labels`` (B,) int64 on the GPU: the conditional
+    step of fgan128_cond_complete.py:296-308 over FCondGenerator / FCondDiscriminator,
+    loss_G = hinge_loss_gen(D(G(z, labels), labels))."""
     G.requires_grad_(True)
     D.requires_grad_(False)
     optim_D.zero_grad()
     optim_G.zero_grad()
-    fake = G(z, noises)
-    loss_G = hinge_loss_gen(D(fake))
+    if labels is None:
+        fake = G(z, noises)
+        loss_G = hinge_loss_gen(D(fake))
+    else:
+        fake = G(z, labels, noises)
+        loss_G = hinge_loss_gen(D(fake, labels))
     loss_G.backward()
     optim_G.step()
     return loss_G
 
 
-def discriminator_step(G, D, optim_G, optim_D, z, real, noises=None):
+def discriminator_step(G, D, optim_G, optim_D, z, real, noises=None, labels=None):
     """fgan128_complete.py:692-703 (one of num_dis_updates): G frozen (its forward takes the
     no-grad inference path), loss_D = hinge_loss_dis(D(G(z)), D(real)) in the reference's call order,
-    backward into D, optim_D.step()."""
+    backward into D, optim_D.step().  ``labels``: the conditional step of
+    fgan128_cond_complete.py:311-324, the real batch's labels on both critic calls."""
     G.requires_grad_(False)
     D.requires_grad_(True)
     optim_D.zero_grad()
     optim_G.zero_grad()
-    fake = G(z, noises)
-    output_dg = D(fake)
-    output_dreal = D(real)
+    if labels is None:
+        fake = G(z, noises)
+        output_dg = D(fake)
+        output_dreal = D(real)
+    else:
+        fake = G(z, labels, noises)
+        output_dg = D(fake, labels)
+        output_dreal = D(real, labels)
     loss_D = hinge_loss_dis(output_dg, output_dreal)
     loss_D.backward()
     optim_D.step()
     return loss_D
 
 
-def train_iteration(G, D, optim_G, optim_D, z_g, z_d, real, num_dis_updates=1):
+def train_iteration(G, D, optim_G, optim_D, z_g, z_d, real, num_dis_updates=1, labels=None):
     """one iteration of the reference's loop body (:680-703) without its logging / LR schedule:
     a generator update, then ``num_dis_updates`` discriminator updates (z_d: one z per update)"""
-    loss_G = generator_step(G, D, optim_G, optim_D, z_g)
+    loss_G = generator_step(G, D, optim_G, optim_D, z_g, labels=labels)
     zs = z_d if isinstance(z_d, (list, tuple)) else [z_d]
     assert len(zs) == num_dis_updates
     loss_D = None
     for z in zs:
-        loss_D = discriminator_step(G, D, optim_G, optim_D, z, real)
+        loss_D = discriminator_step(G, D, optim_G, optim_D, z, real, labels=labels)
     return loss_G, loss_D

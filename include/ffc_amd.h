@@ -621,6 +621,41 @@ int ffc_pool2(const float* x, long long P, int H, int W, float scale, float* y, 
  * (spectral_transform.py:44-45), the adjoint of AvgPool2d(2,2) with scale 0.25 */
 int ffc_up2(const float* x, long long P, int h, int w, float scale, float* y, void* stream);
 
+/* ------------------------------------------------------------------ class-conditional fgan128
+ * fgan128_cond_complete.py:33-180 (FCondGenerator, label-conditioned Discriminator).  labels: int64
+ * DEVICE tensor (B), read by the kernels (no host read: a captured step replays with new labels in the
+ * same buffer).  A label outside [0, num_classes) touches no memory outside the table: its gathered
+ * row is NaN and it contributes nothing to a scatter.  Pure additions: the ABI version is unchanged. */
+/* Generator stem (:91-101) up to the BatchNorm apply:
+ *   out[b][0:256]   = ConvTranspose2d(z_size, 256, 4, 1, 0)(z[b])  = z[b] . w_in + bias_in
+ *   out[b][256:512] = ConvTranspose2d(num_classes, 256, 4, 1, 0)(label_embed[labels[b]])
+ * out (B, 512, 4, 4) = torch.cat([input, embedding], 1) before the two BatchNorm2d(256) + GELU;
+ * weights in nn.ConvTranspose2d layout (K, 256, 4, 4), label_embed (num_classes, num_classes); exact
+ * fp32 products (v_mfma_f32_32x32x2_f32).  slab (NULL in eval mode): BN partial rows {n, mean, M2, -}
+ * (float4) as two consecutive slabs [ffc_cond_stem_slab_rows(B)][256], input branch then label branch,
+ * for ffc_bn_reduce_finalize(_batch). */
+int ffc_cond_stem_slab_rows(int B);
+int ffc_cond_stem_forward(const float* z, const int64_t* labels, const float* label_embed, const float* w_in,
+                          const float* bias_in, const float* w_label, const float* bias_label, int B, int z_size,
+                          int num_classes, float* out, float* slab, void* stream);
+/* Backward of ffc_cond_stem_forward from dpre = d out (B, 512, 4, 4): dw_in (z_size, 256, 4, 4),
+ * dbias_in (256), dw_label (num_classes, 256, 4, 4), dbias_label (256), dz (B, z_size),
+ * dlabel_embed (num_classes, num_classes); any of them may be NULL (not computed).  dlabel_embed needs
+ * ws: B * num_classes floats.  Deterministic: every sum runs over the samples in a fixed order, no
+ * atomics; rows of classes absent from the batch are exact zeros.  z_size, num_classes <= 1024. */
+int ffc_cond_stem_backward(const float* dpre, const float* z, const int64_t* labels, const float* label_embed,
+                           const float* w_in, const float* w_label, int B, int z_size, int num_classes, float* dw_in,
+                           float* dbias_in, float* dw_label, float* dbias_label, float* dz, float* dlabel_embed,
+                           float* ws, void* stream);
+/* nn.Embedding(num_classes, D) row lookup (the critic's 128x128 label plane, :159-163):
+ * out[b][:] = table[labels[b]][:], 16-byte accesses when D % 4 == 0 and the tensors are aligned */
+int ffc_embed_gather_rows(const float* table, const int64_t* labels, int B, int num_classes, int D, float* out,
+                          void* stream);
+/* its weight gradient: dtable[c][:] = sum of grad[b][:] over the samples with labels[b] == c, in
+ * sample order (bitwise reproducible); zeros for absent classes */
+int ffc_embed_scatter_rows(const float* grad, const int64_t* labels, int B, int num_classes, int D, float* dtable,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
