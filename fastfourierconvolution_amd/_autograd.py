@@ -608,7 +608,7 @@ def linear(lin: nn.Linear, z):
 # --------------------------------------------------------------------------- FFTs
 def rfft2_impl(x, mirror_scale):
     """ffc::rfft2: interleave(rfftn(x, ortho)) -> (B, 2C, H, W/2+1), mirrored bins x mirror_scale
-    (0.5: the adjoint of irfftn)"""
+    (2: the adjoint of irfftn at scale 1, which ffc::irfft2's backward runs)"""
     x = rt.require(x, "x")
     B, C, H, W = x.shape
     Z = torch.empty((B, 2 * C, H, W // 2 + 1), device=x.device, dtype=torch.float32)
@@ -620,7 +620,7 @@ def rfft2_impl(x, mirror_scale):
 
 def irfft2_impl(Z, H, W, mirror_scale, r):
     """ffc::irfft2: irfftn(deinterleave(Z), s=(H, W), ortho) [+ r], mirrored bins x mirror_scale
-    (2: the adjoint of rfftn)"""
+    (0.5: the adjoint of rfftn at scale 1, which ffc::rfft2's backward runs)"""
     Z = rt.require(Z, "Z")
     B, C2 = Z.shape[:2]
     y = torch.empty((B, C2 // 2, H, W), device=Z.device, dtype=torch.float32)
