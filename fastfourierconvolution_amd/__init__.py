@@ -4,20 +4,22 @@
 
 exports FourierUnitSN, SELayer, SpectralTransform, FFC, FFCTranspose, FFC_BN_ACT, SNFFC, SNFFCTranspose
 (layers/snffc), Resizer,
-Print, debug_print, NoiseInjection (the names layers/__init__.py:2-18 exports for this path)
-plus the restated callers FFCModel / FFCGenerator / FFCDiscriminator / FGenerator and Discriminator (fgan128) and the
-class-conditional FCondGenerator / FCondDiscriminator (fgan128_cond_complete.py).  All compute runs in
+Print, debug_print, NoiseInjection, GaussianNoise (the names layers/__init__.py:2-18 exports for this path)
+plus the restated callers FFCModel / FFCGenerator / FFCDiscriminator / FGenerator and Discriminator (fgan128), the
+class-conditional FCondGenerator / FCondDiscriminator (fgan128_cond_complete.py) and the 8*mg family
+FGenerator32 / Discriminator32 / FDiscriminator32 (fgan_complete.py; 32x32 at mg = 4, 48x48 at mg = 6).  All compute runs in
 the gfx950 HIP library libffc_amd.so (include/ffc_amd.h); there is no CPU fallback.
 """
 from . import ops  # noqa: F401  (registers the torch.ops.ffc.* custom ops)
 from .config import Config
 from .ffc import (FFC, FFC_BN_ACT, SNFFC, FFCTranspose, FourierUnitSN, SELayer, SNFFCTranspose, SpectralTransform,
                   set_mix_precision, spectral_norm_ffc)
-from .layers_misc import NoiseInjection, Print, Resizer, debug_print
-from .models import (Discriminator, FCondDiscriminator, FCondGenerator, FFCDiscriminator, FFCGenerator, FFCModel,
-                     FGanDiscriminator, FGenerator)
+from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
+from .models import (Discriminator, Discriminator32, FCondDiscriminator, FCondGenerator, FDiscriminator32,
+                     FFCDiscriminator, FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32)
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
            "SNFFCTranspose", "spectral_norm_ffc", "set_mix_precision", "Resizer",
            "Print", "debug_print", "NoiseInjection", "FFCModel", "FFCGenerator", "FFCDiscriminator", "FGenerator",
-           "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "Config"]
+           "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "FGenerator32",
+           "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config"]

@@ -245,7 +245,8 @@ __global__ __launch_bounds__(FU_THREADS) void fu_kernel(FuArgs a) {
         __syncthreads();
     } else {
 
-    if (a.shuf) {
+    if (is_pow2c(H) && a.shuf) {   // the lane columns exist for 2^k rows only: nothing of them compiles otherwise
+        if constexpr (is_pow2c(H)) {
         // 1+2. row R2C in registers, then the column DFTs across the H lanes that hold the channel's
         //      rows (lane_fft_dif: DPP / ds_swizzle butterfly exchanges, ortho scale folded in): no LDS
         //      round trip and no barrier between the row and column transforms.  Lane y ends with
@@ -269,6 +270,7 @@ __global__ __launch_bounds__(FU_THREADS) void fu_kernel(FuArgs a) {
         if (a.wm_lds) ffc::dma_wait();
         __syncthreads();
         FU_STAMP(2);
+        }   // is_pow2c(H)
     } else {
     // 1. row R2C (real W-point FFT per (channel,row) on a W/2-point complex FFT), input transform fused
     for (int r = tid; r < C * H; r += FU_THREADS) {
@@ -422,7 +424,8 @@ __global__ __launch_bounds__(FU_THREADS) void fu_kernel(FuArgs a) {
         if (tid == 0) g_fu_trace[8 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
 #endif
         return;
-    } else if (a.shuf) {
+    } else if (is_pow2c(H) && a.shuf) {
+        if constexpr (is_pow2c(H)) {
         // 4+5. lane y reads spectrum row bitrev(y), the inverse column DFTs run across the channel's H
         //      lanes (lane_ifft_dit, ortho scale folded in) and leave row y in lane y for its C2R
         for (int r = tid; r < C * H; r += FU_THREADS) {
@@ -446,6 +449,7 @@ __global__ __launch_bounds__(FU_THREADS) void fu_kernel(FuArgs a) {
             }
             store_row<W>(a.out + ((size_t)(b * C + ch) * H + y) * W, re);
         }
+        }   // is_pow2c(H)
     } else {
         // 4. inverse column C2C over H, ortho scale
         for (int q = tid; q < C * WP; q += FU_THREADS) {
@@ -851,11 +855,18 @@ FuKernel pick_kernel(int H, int W, int up, int pass) {
         case 8: return pick_w<8>(W, up, pass);
         case 16: return pick_w<16>(W, up, pass);
         case 32: return pick_w<32>(W, up, pass);
+        // 3 * 2^k planes (the mg = 6 models), mixed-radix row / column FFTs (fft_reg.h): square 24 at up 1
+        // and 2, square 48 as the x2-upsampled output of a SpectralTransform only (up = 2, t at 24)
+        case 24: return W == 24 ? pick_up_pass<24, 24>(up, pass) : nullptr;
+        case 48: return W == 48 && up == 2 ? (pass == 0 ? fu_kernel<48, 48, 2, 0> : fu_kernel<48, 48, 2, 1>) : nullptr;
     }
     return nullptr;
 }
 
 bool pow2_in(int v, int lo, int hi) { return v >= lo && v <= hi && (v & (v - 1)) == 0; }
+// planes of the fused kernel: H, W powers of two in [4, 32] or square 24 (up 1 or 2), or square 48 (up = 2)
+bool fu_plane3(int H, int W) { return H == W && (H == 24 || H == 48); }
+bool fu_plane_ok(int H, int W) { return (pow2_in(H, 4, 32) && pow2_in(W, 4, 32)) || fu_plane3(H, W); }
 
 template <int H, int W, int UP>
 FuKernel pick_split_g(int kgroups) {
@@ -977,8 +988,13 @@ extern "C" int ffc_debug_fu_trace_read(void* dst, size_t bytes) {
 #endif
 
 extern "C" size_t ffc_fu_lds_bytes(int C, int H, int W) {
-    if (C <= 0 || C > 4096 || !pow2_in(H, 4, 32) || !pow2_in(W, 4, 32)) return 0;   // C > 4096 never fits LDS
+    if (C <= 0 || C > 4096 || !fu_plane_ok(H, W)) return 0;   // C > 4096 never fits LDS
     return fu_layout(C, H, W).bytes;
+}
+
+extern "C" int ffc_fu_supported(int C, int H, int W, int up) {
+    if (!(up == 1 || up == 2) || ffc_fu_lds_bytes(C, H, W) == 0) return 0;
+    return H == 48 ? up == 2 : 1;
 }
 
 extern "C" int ffc_fu_forward(const float* t, int B, int C, int H, int W, int up, const float* in_scale,
@@ -1092,8 +1108,9 @@ static int fu_forward_impl(const float* t, int B, int C, int H, int W, int up, c
     if (fu_mix_f32_forced() || C % 8 != 0) wmix3 = nullptr;
     const bool packed = wmix3 != nullptr;
     const size_t lds = ffc_fu_lds_bytes(C, H, W) > 0 ? fu_layout(C, H, W, packed).bytes : 0;
-    FFC_CHECK_ARG(lds > 0, "ffc_fu_forward: unsupported (C,H,W): H,W must be powers of two in [4,32] "
-                           "and 16*C*H*(W/2+1) <= 160 KiB");
+    FFC_CHECK_ARG(lds > 0, "ffc_fu_forward: unsupported (C,H,W): H,W must be powers of two in [4,32] or "
+                           "H = W in {24,48}, and 16*C*H*(W/2+1) <= 160 KiB");
+    FFC_CHECK_ARG(H != 48 || up == 2, "ffc_fu_forward: unsupported: 48x48 planes need up = 2");
     FFC_CHECK_ARG(t && wmixT, "ffc_fu_forward: null input");
     FFC_CHECK_ARG((in_scale == nullptr) == (in_shift == nullptr), "ffc_fu_forward: in_scale/in_shift pairing");
     if (pass == 0) FFC_CHECK_ARG(stats_slab != nullptr, "ffc_fu_forward: pass 0 needs stats_slab");
@@ -1148,7 +1165,7 @@ static int fu_forward_impl(const float* t, int B, int C, int H, int W, int up, c
     a.mgroups = 1;
     a.B = B;
     a.kgroups = kgroups;
-    a.shuf = fu_shuf_on() && H >= 2 && H <= 32 ? 1 : 0;
+    a.shuf = fu_shuf_on() && pow2_in(H, 2, 32) ? 1 : 0;   // lane columns: power-of-two H only
     if (pass == 0 && kgroups == 2) {
         // pass 0 over two bin groups per sample (fu_pass0_kg_kernel): the split weight staged in LDS
         // while two workgroups still fit a CU, else read from L2

@@ -75,7 +75,7 @@ class FourierUnitSN(nn.Module):
         H, W = th * up, tw * up
         self._check(C)
         L = rt.lib()
-        fused = L.ffc_fu_lds_bytes(C, H, W) > 0 and not rt.FORCE_FU2D
+        fused = L.ffc_fu_supported(C, H, W, up) == 1 and not rt.FORCE_FU2D
         staged_ok = L.ffc_fu2d_supported(C, H, W, up)
         if self.mix_precision == "fp16":
             if not (staged_ok and C in (16, 32, 64)):
@@ -90,8 +90,10 @@ class FourierUnitSN(nn.Module):
         if not fused:
             if L.ffc_fu2d_supported(C, H, W, up):
                 return self._run2d(t, up, in_scale, in_shift, in_relu, residual, in_fold)
-            raise NotImplementedError(f"Fourier unit supports H,W in {{4,8,16,32}} with 16*C*H*(W/2+1) <= 160 KiB "
-                                      f"(fused) or square H=W in {{16,32,64,128}} with 2C <= 128 (staged); "
+            raise NotImplementedError(f"Fourier unit supports H,W in {{4,8,16,32}}, square 24x24, or 48x48 as "
+                                      f"the x2-upsampled output of a SpectralTransform (up = 2), with "
+                                      f"16*C*H*(W/2+1) <= 160 KiB (fused), "
+                                      f"or square H=W in {{16,32,64,128}} with 2C <= 128 (staged); "
                                       f"got C={C}, {H}x{W}")
         dev = t.device
         stream = rt.stream_of(t)

@@ -1,5 +1,6 @@
 """Caller helpers of the FFC block: Resizer (layers/resizer.py:10-24), Print / debug_print
-(layers/print_layer.py:10-32), NoiseInjection (layers/noise_injection.py:20-32).
+(layers/print_layer.py:10-32), NoiseInjection (layers/noise_injection.py:20-32), GaussianNoise
+(layers/gaussian_noise.py:6-15).
 
 Resizer / Print only move tuples around or print shapes.  NoiseInjection's add (fgan128 train
 mode) runs in the HIP library (the ffc::noise_inject op); the noise itself is drawn with torch's device
@@ -62,3 +63,27 @@ class NoiseInjection(nn.Module):
         from . import _autograd as ag
         from . import _runtime as rt
         return ag.noise_inject(self, rt.require(x, "x"), noise)
+
+
+class GaussianNoise(nn.Module):
+    """layers/gaussian_noise.py:6-15: x + N(0, stddev) in train mode, the identity in eval mode.  The add
+    runs on the ffc::noise_inject op with every (sample, channel) plane as a one-channel sample of its
+    own: weight = stddev, unit-variance noise of x's shape drawn with normal_() as the reference draws
+    it.  x: (B, C, H, W) fp32 on the GPU, H*W % 4 == 0."""
+
+    def __init__(self, stddev):
+        super().__init__()
+        self.stddev = stddev
+
+    def forward(self, x):
+        if not self.training:
+            return x
+        from . import _runtime as rt
+        x = rt.require(x, "x")
+        if x.dim() != 4:
+            raise NotImplementedError("GaussianNoise: x must be (B, C, H, W)")
+        B, C, H, W = x.shape
+        noise = x.new_empty(B * C, 1, H, W).normal_()
+        weight = x.new_full((1, 1, 1, 1), float(self.stddev))
+        planes = x.contiguous().view(B * C, 1, H, W)   # a strided x is copied once, here
+        return torch.ops.ffc.noise_inject(planes, weight, noise).reshape(B, C, H, W)

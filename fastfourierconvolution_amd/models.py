@@ -6,6 +6,10 @@ FFCDiscriminator (models/ffc_discriminator.py:11-58), the fgan128 FGenerator
 trained against (fgan128_complete.py:525-562).  The layer stacks are identical; the
 only change is that the ``inplanes=`` keyword the reference callers pass (and its base class
 rejects, models/ffcmodel.py:17) is accepted and ignored.
+
+The 8*mg family of fgan_complete.py (32x32 at mg = 4; 48x48 STL-10 / flowers / CelebA at mg = 6) is
+restated as FGenerator32, Discriminator32 and FDiscriminator32: ``FGenerator`` and ``Discriminator``
+name the fgan128 classes here.
 """
 import os
 
@@ -18,7 +22,7 @@ from ._lib import check, ptr
 from . import _plan
 from .config import Config
 from .ffc import FFC_BN_ACT
-from .layers_misc import NoiseInjection, Print, Resizer, debug_print
+from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
 
 # FGenerator conv6 -> conv7 hand-off with the BN + GELU + noise pass deferred into the head's operand
 # staging (FFC_DEFER_HEAD=0: the separate pass, for A/B runs).  The head is VALU-bound, so the
@@ -133,6 +137,10 @@ class FGenerator(FFCModel):
     [(lcl, glb)] * 5 ((B, 1, H, W) each) instead of drawing it (the reference draws it inside
     NoiseInjection with normal_()); the reference's forward(z) is the noises=None call."""
 
+    UPS = (2, 3, 4, 5, 6)   # conv{n}: the x2 FFC_BN_ACT + NoiseInjection layers of the trunk
+    HEAD = 7                # conv{HEAD}: the 3x3 Tanh head
+    USES_SN = True          # the uses_sn flag the reference passes to its FFC_BN_ACTs (stored, unused)
+
     def __init__(self, z_size, mg: int = 4):
         super().__init__()
         self.z_size = z_size
@@ -145,17 +153,19 @@ class FGenerator(FFCModel):
 
     def _build_trunk(self, ngf, ratio_g):
         """conv2..conv6 (x2 FFC_BN_ACT + NoiseInjection pairs) and the conv7 head at width ngf and global
-        ratio ratio_g (fgan128_complete.py:457-488; fgan128_cond_complete.py:43-70 at ngf = 64, 0.25)"""
+        ratio ratio_g (fgan128_complete.py:457-488; fgan128_cond_complete.py:43-70 at ngf = 64, 0.25);
+        conv2..conv4 and the conv5 head for the 8*mg family (UPS / HEAD; fgan_complete.py:97-113)"""
         T = dict(activation_layer=nn.GELU, norm_layer=nn.BatchNorm2d, upsampling=True, uses_noise=True,
-                 uses_sn=True)
+                 uses_sn=self.USES_SN)
         plan = ((2, ngf * 8, ngf * 4, 0.0), (3, ngf * 4, ngf * 2, ratio_g), (4, ngf * 2, ngf, ratio_g),
-                (5, ngf, ngf, ratio_g), (6, ngf, ngf, ratio_g))
+                (5, ngf, ngf, ratio_g), (6, ngf, ngf, ratio_g))[:len(self.UPS)]
         for n, cin, cout, rin in plan:
             setattr(self, f"conv{n}", FFC_BN_ACT(cin, cout, 4, rin, ratio_g, stride=2, padding=1, **T))
             setattr(self, f"lcl_noise{n}", NoiseInjection(int(cout * (1 - ratio_g))))
             setattr(self, f"glb_noise{n}", NoiseInjection(int(cout * ratio_g)))
-        self.conv7 = FFC_BN_ACT(ngf, 3, 3, ratio_g, 0.0, stride=1, padding=1, activation_layer=nn.Tanh,
-                                norm_layer=nn.Identity, upsampling=False, uses_noise=True, uses_sn=True)
+        setattr(self, f"conv{self.HEAD}",
+                FFC_BN_ACT(ngf, 3, 3, ratio_g, 0.0, stride=1, padding=1, activation_layer=nn.Tanh,
+                           norm_layer=nn.Identity, upsampling=False, uses_noise=True, uses_sn=self.USES_SN))
 
     def _noise_to_feature(self, z):
         """nn.Linear(z_size, 16*1024) (fgan128_complete.py:453-455) on the HIP dense GEMM"""
@@ -171,18 +181,18 @@ class FGenerator(FFCModel):
     def _trunk(self, fake, noises=None):
         """conv2..conv7 + Resizer on the (B, C, 4, 4) stem output (:496-515); shared with FCondGenerator"""
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        for i, n in enumerate((2, 3, 4, 5, 6)):                              # :496-515
+        for i, n in enumerate(self.UPS):                                     # :496-515
             conv = getattr(self, f"conv{n}")
             # conv6 -> conv7: conv6's BN + GELU (+ noise) is applied by the 3x3 head as it stages its
             # input (ffc_conv3x3_smallm_tf), no separate pass over the 128x128 activations
-            defer = n == 6 and not grad and DEFER_HEAD_INPUT
+            defer = n == self.UPS[-1] and not grad and DEFER_HEAD_INPUT
             if self.training:   # NoiseInjection fused into conv{n}'s BN + GELU pass
                 nl, ng = noises[i] if noises is not None else (None, None)
                 nzl, nzg = (getattr(self, f"lcl_noise{n}"), nl), (getattr(self, f"glb_noise{n}"), ng)
                 fake = conv.forward_deferred(fake, nzl, nzg) if defer else conv.forward_noise(fake, nzl, nzg)
             else:
                 fake = conv.forward_deferred(fake) if defer else conv(fake)
-        return self.resizer(self.conv7(fake))
+        return self.resizer(getattr(self, f"conv{self.HEAD}")(fake))
 
     def forward_float(self, z, noises=None):
         """FGenerator.forward up to the float image (:491-515): the eval-mode uint8 quantization of
@@ -210,6 +220,7 @@ class Discriminator(FFCModel):
 
     CONVS = ((3, 64, 3, 1), (64, 64, 4, 2), (64, 128, 3, 1), (128, 128, 4, 2), (128, 256, 3, 1),
              (256, 256, 4, 2), (256, 512, 3, 1), (512, 512, 4, 2), (512, 512, 4, 2))
+    SIDE = 32   # input side per unit of mg (the stride-2 convs of CONVS take it down to mg)
 
     def __init__(self, sn: bool = True, mg: int = 4):
         super().__init__()
@@ -223,9 +234,9 @@ class Discriminator(FFCModel):
 
     def forward(self, x):
         x = rt.require(x, "x")
-        side = 32 * self.mg
+        side = self.SIDE * self.mg
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, side, side):
-            raise RuntimeError(f"Discriminator: x must be (B, 3, {side}, {side}), got {tuple(x.shape)}")
+            raise RuntimeError(f"{type(self).__name__}: x must be (B, 3, {side}, {side}), got {tuple(x.shape)}")
         act, param = rt.act_code(self.act)
         m = x
         for i in range(1, len(self.CONVS) + 1):
@@ -237,6 +248,74 @@ class Discriminator(FFCModel):
 
 
 FGanDiscriminator = Discriminator
+
+
+class FGenerator32(FGenerator):
+    """fgan_complete.py:81-140, the generator of the 8*mg family (CIFAR-10 at mg = 4, the 48x48 STL-10 /
+    flowers / CelebA models at mg = 6): Linear(z, mg*mg*512) -> (512, mg, mg) -> three x2 FFC_BN_ACT
+    (FFCTranspose, BatchNorm2d + GELU, train-mode NoiseInjection on both branches) at ngf = 64, global
+    ratio 0.25 -> 3x3 FFC_BN_ACT head conv5 (Tanh) -> Resizer; eval mode returns the uint8 image of
+    :136-138 (its clamp to [-1, 1] is the identity on a Tanh output).  FGenerator's trunk with three
+    layers; constructor, attribute names and state_dict keys are the reference FGenerator's.
+
+    ``forward(z, noises=None)``: ``noises`` as FGenerator, [(lcl, glb)] * 3."""
+
+    UPS = (2, 3, 4)
+    HEAD = 5
+    USES_SN = False
+
+    def __init__(self, z_size, mg: int = 4):
+        FFCModel.__init__(self)
+        self.z_size = z_size
+        self.ngf = 64
+        ratio_g = 0.25
+        self.mg = mg
+        self.noise_to_feature = nn.Sequential(nn.Linear(z_size, (self.mg * self.mg) * self.ngf * 8))
+        self._build_trunk(self.ngf, ratio_g)
+
+
+class Discriminator32(Discriminator):
+    """fgan_complete.py:142-171: the plain spectral-norm critic of the 8*mg family, conv1..conv7 of
+    Discriminator (three stride-2 convs: 8*mg -> mg) and fc = Linear(mg*mg*512, 1); no ``last_act``.
+    Input: (B, 3, 8*mg, 8*mg) fp32 on the GPU."""
+
+    CONVS = Discriminator.CONVS[:7]
+    SIDE = 8
+
+    def __init__(self, sn: bool = True, mg: int = 4):
+        super().__init__(sn=sn, mg=mg)
+        del self.last_act
+
+
+class FDiscriminator32(FFCModel):
+    """fgan_complete.py:173-214: the FFC critic of the 8*mg family.  ``main`` is four FFC_BN_ACT with
+    bias, global ratio 0 (local branch only: a 3x3 s1 conv and three 4x4 s2 convs, one implicit-GEMM
+    launch each), LeakyReLU(0.1), BatchNorm2d on the last three; fc = Linear(mg*mg*512, 1) under spectral
+    norm when ``sn``.  ``gaus_noise`` is built and, as in the reference (:206), not used by forward.
+    Input: (B, 3, 8*mg, 8*mg) fp32 on the GPU."""
+
+    def __init__(self, sn: bool = True, mg: int = 4):
+        super().__init__()
+        self.mg = mg
+        sn_fn = torch.nn.utils.spectral_norm if sn else (lambda m: m)
+        L = dict(ratio_gin=0, ratio_gout=0.0, padding=1, bias=True, uses_noise=False, uses_sn=True,
+                 activation_layer=nn.LeakyReLU)
+        self.main = nn.Sequential(
+            FFC_BN_ACT(in_channels=3, out_channels=64, kernel_size=3, stride=1, norm_layer=nn.Identity, **L),
+            FFC_BN_ACT(in_channels=64, out_channels=128, kernel_size=4, stride=2, norm_layer=nn.BatchNorm2d, **L),
+            FFC_BN_ACT(in_channels=128, out_channels=256, kernel_size=4, stride=2, norm_layer=nn.BatchNorm2d, **L),
+            FFC_BN_ACT(in_channels=256, out_channels=512, kernel_size=4, stride=2, norm_layer=nn.BatchNorm2d, **L))
+        self.fc = sn_fn(nn.Linear(self.mg * self.mg * 512, 1))
+        self.gaus_noise = GaussianNoise(0.05)
+
+    def forward(self, x):
+        x = rt.require(x, "x")
+        side = 8 * self.mg
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, side, side):
+            raise RuntimeError(f"FDiscriminator32: x must be (B, 3, {side}, {side}), got {tuple(x.shape)}")
+        self.print_size(x)
+        m = self.resizer(self.main(x))                                           # :208-209
+        return ag.linear(self.fc, m.reshape(-1, self.mg * self.mg * 512))        # :214
 
 
 class FCondGenerator(FGenerator):

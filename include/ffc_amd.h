@@ -389,7 +389,11 @@ int ffc_conv3x3_smallm_tf(const float* x0, int C0, const float* w0, const float*
  *   pass 0: write per-sample BN partials of Y to stats_slab [B][2C] float4
  *   pass 1: out = (residual ? s : 0) + irfftn(relu(Y*bn_scale + bn_shift), s=(H,W), ortho)
  * wmixT: (2C, Mpad) transposed, zero-padded copy of conv_layer.weight (Mpad = ceil32(2C)).
- * H, W: powers of two in [4, 32] (the sizes of the FFC-DCGAN generator/discriminator). */
+ * H, W: powers of two in [4, 32] (the sizes of the FFC-DCGAN generator/discriminator), or square
+ * H = W = 24 (up 1 or 2) and H = W = 48 with up = 2 (the Fourier units of the mg = 6 models, reached
+ * as the x2-upsampled output of a transposed SpectralTransform; one radix-3 stage under the radix-2
+ * stages of the register FFTs).  These run fu_kernel only: ffc_fu_kgroups answers 1 for them, pass 1 from a spill
+ * runs one workgroup per sample, and FFC_FU_SHUF does not apply. */
 int ffc_fu_forward(const float* t, int B, int C, int H, int W, int up, const float* in_scale,
                    const float* in_shift, int in_relu, const float* wmixT, int pass,
                    float* stats_slab, const float* bn_scale, const float* bn_shift,
@@ -398,6 +402,8 @@ int ffc_fu_forward(const float* t, int B, int C, int H, int W, int up, const flo
 int ffc_fu_pack_mix(const float* w, int C2, float* wmixT, void* stream);
 /* LDS bytes the fused FU kernel needs (0 if unsupported) */
 size_t ffc_fu_lds_bytes(int C, int H, int W);
+/* 1 when ffc_fu_forward* takes (C, H, W) at this `up`: ffc_fu_lds_bytes > 0, and up = 2 on the 48 x 48 plane */
+int ffc_fu_supported(int C, int H, int W, int up);
 
 /* A train-mode BatchNorm finalized inside the kernel that applies it (single rank: no all-reduce
  * between the batch-statistics merge and the finalize).  Each workgroup of the consumer merges
