@@ -165,36 +165,33 @@ def test_conv3x3_smallm_tf_abi_validation():
 @pytest.mark.parametrize("C0,C1,M,H,W,noise,act", [(16, 0, 1, 40, 24, True, 5), (6, 5, 4, 33, 20, False, 2),
                                                   (64, 64, 3, 128, 128, True, 5), (8, 8, 2, 72, 96, True, 1)])
 def test_conv3x3_smallm_tf_ragged(C0, C1, M, H, W, noise, act):
-    """ffc_conv3x3_smallm_tf on ragged tiles / one or two segments against torch: transform
-    (act(x*scale + shift) + noise_w * noise, zero padding outside) then Conv2d 3x3 p1 + Tanh"""
+    """ffc_conv3x3_smallm_tf on ragged tiles / one or two segments against the float64 reference
+    (tests/conv_refs.py conv3x3_ref): transform (act(x*scale + shift) + noise_w * noise, zero padding
+    outside) then Conv2d 3x3 p1 + Tanh"""
     import ctypes
-    import torch.nn.functional as Fn
+    import conv_refs as cr
     from fastfourierconvolution_amd import _lib
     L = _lib.load()
     g = torch.Generator().manual_seed(C0 * 7 + H)
     B = 2
-    xs = [torch.randn((B, c, H, W), generator=g).cuda() for c in (C0, C1) if c]
-    ws = [(torch.randn((M, c, 3, 3), generator=g) / (9 * c) ** 0.5).cuda() for c in (C0, C1) if c]
-    tfs, keep, xt = [], [], []
+    xs = [torch.randn((B, c, H, W), generator=g) for c in (C0, C1) if c]
+    ws = [torch.randn((M, c, 3, 3), generator=g) / (9 * c) ** 0.5 for c in (C0, C1) if c]
+    tfs, keep, refs = [], [], []
     for x in xs:
-        C = x.shape[1]
-        sc = (1 + 0.2 * torch.randn(C, generator=g)).cuda()
-        sh = (0.1 * torch.randn(C, generator=g)).cuda()
-        nw = torch.randn(C, generator=g).cuda() if noise else None
-        nz = torch.randn((B, 1, H, W), generator=g).cuda() if noise else None
-        keep += [sc, sh, nw, nz]
-        tfs.append(_lib.InTf(sc.data_ptr(), sh.data_ptr(), act, 0.1, nw.data_ptr() if noise else None,
-                             nz.data_ptr() if noise else None))
-        y = x * sc[None, :, None, None] + sh[None, :, None, None]
-        y = {5: Fn.gelu, 2: lambda v: Fn.leaky_relu(v, 0.1), 1: torch.relu}[act](y)
-        if noise:
-            y = y + nw[None, :, None, None] * nz
-        xt.append(y)
-    out = torch.empty((B, M, H, W), device="cuda")
-    rc = L.ffc_conv3x3_smallm_tf(xs[0].data_ptr(), C0, ws[0].data_ptr(), xs[1].data_ptr() if C1 else None, C1,
-                                 ws[1].data_ptr() if C1 else None, None, B, H, W, M, out.data_ptr(), 3, 0.0,
+        t = cr.tf_inputs(B, x.shape[1], H, W, act, noise, g)
+        refs.append(t)
+        dev = {k: t[k].cuda() for k in ("scale", "shift", "noise_w", "noise") if t[k] is not None}
+        keep.append(dev)
+        tfs.append(_lib.InTf(dev["scale"].data_ptr(), dev["shift"].data_ptr(), act, 0.1,
+                             dev["noise_w"].data_ptr() if noise else None, dev["noise"].data_ptr() if noise else None))
+    xd, wd = [x.cuda() for x in xs], [w.cuda() for w in ws]
+    out = torch.full((B, M, H, W), float("nan"), device="cuda")
+    rc = L.ffc_conv3x3_smallm_tf(xd[0].data_ptr(), C0, wd[0].data_ptr(), xd[1].data_ptr() if C1 else None, C1,
+                                 wd[1].data_ptr() if C1 else None, None, B, H, W, M, out.data_ptr(), 3, 0.0,
                                  ctypes.byref(tfs[0]), ctypes.byref(tfs[1]) if C1 else None, None)
     assert rc == 0, L.ffc_last_error()
     torch.cuda.synchronize()
-    ref = sum(Fn.conv2d(y.double(), w.double(), padding=1) for y, w in zip(xt, ws)).tanh()
-    assert normwise_err(out.cpu(), ref.cpu()) <= 1e-5
+    assert not torch.isnan(out).any()
+    ref = cr.conv3x3_ref(xs[0], ws[0], xs[1] if C1 else None, ws[1] if C1 else None, None, 3, 0.0, refs[0],
+                         refs[1] if C1 else None)
+    assert normwise_err(out.cpu(), ref) <= 1e-5
