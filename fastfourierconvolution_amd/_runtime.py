@@ -9,6 +9,7 @@ sharded train-mode batches) and the launches themselves.  Every launch goes to
 from __future__ import annotations
 
 import ctypes
+import os
 
 import torch
 import torch.nn as nn
@@ -36,6 +37,17 @@ def stream_of(t: torch.Tensor) -> int:
 
 def lib():
     return _lib.load()
+
+
+def _env(var: str, default: str, parse=str):
+    """value of a module-level switch: parse(the environment's ``var``, or ``default`` when unset).  The
+    result is bound to a plain module attribute (tests and tools assign those); one a plan depends on is
+    also named in PLAN_KNOBS below."""
+    return parse(os.environ.get(var, default))
+
+
+def _not0(s: str) -> bool:
+    return s != "0"
 
 
 # --------------------------------------------------------------------------- launch observer
@@ -252,13 +264,13 @@ def bn_scale_shift_many(items, device, stream):
 # Train-mode BNs whose consumer kernel finalizes them in-kernel (ffc_bn_fold) instead of a
 # separate ffc_bn_reduce_finalize launch: single rank only (SyncBN all-reduces the moments between
 # the merge and the finalize).  FFC_BN_FOLD=0 restores the separate launch (A/B measurements).
-BN_FOLD = __import__("os").environ.get("FFC_BN_FOLD", "1") != "0"
+BN_FOLD = _env("FFC_BN_FOLD", "1", _not0)
 # slab rows x channels up to which the fold beats the separate launch (each consumer workgroup
 # reads the whole slab; measured on MI355X, r02)
-BN_FOLD_MAX = int(__import__("os").environ.get("FFC_BN_FOLD_MAX", "4096"))
+BN_FOLD_MAX = _env("FFC_BN_FOLD_MAX", "4096", int)
 # the SE means of a layer's global input taken from the previous layer's BN-apply pass (plane sums
 # written as it stores y) instead of a second read of y (FFC_SE_SUMS=0: se_mean_kernel)
-SE_SUMS = __import__("os").environ.get("FFC_SE_SUMS", "1") != "0"
+SE_SUMS = _env("FFC_SE_SUMS", "1", _not0)
 
 
 def plane_sums_for(x):
@@ -271,7 +283,7 @@ def plane_sums_for(x):
 
 
 # the fused ST prologue over several workgroups per sample at small batches (FFC_ST_SPLIT=0: one)
-ST_SPLIT = __import__("os").environ.get("FFC_ST_SPLIT", "1") != "0"
+ST_SPLIT = _env("FFC_ST_SPLIT", "1", _not0)
 
 
 def _pow2_floor(v: int) -> int:
@@ -286,8 +298,7 @@ def _pow2_floor(v: int) -> int:
 # (FFC_ST_SPLIT_MAX fixes it for every batch).  Round 6: 4 at B <= 32 -- the per-rank batch of the
 # 8-way strong split -- B = 32 0.1790 / 0.1798 -> 0.1771 / 0.1774 ms (8: 0.1774 / 0.1777), B = 64 level
 # (profiles/r06/st)
-_ST_SPLIT_ENV = __import__("os").environ.get("FFC_ST_SPLIT_MAX")
-ST_SPLIT_MAX = _pow2_floor(_ST_SPLIT_ENV) if _ST_SPLIT_ENV else 0   # 0: by batch (st_split_max)
+ST_SPLIT_MAX = _env("FFC_ST_SPLIT_MAX", "", lambda s: _pow2_floor(s) if s else 0)   # 0: by batch (st_split_max)
 
 
 def st_split_max(B: int) -> int:
@@ -296,9 +307,9 @@ def st_split_max(B: int) -> int:
         return ST_SPLIT_MAX
     return 4 if B <= 32 else 2
 # ST prologue conv1 on the split-bf16 MFMA products (FFC_ST_MFMA=f32: the exact f32-input MFMA, A/B)
-ST_SPLIT_MFMA = __import__("os").environ.get("FFC_ST_MFMA", "split") != "f32"
+ST_SPLIT_MFMA = _env("FFC_ST_MFMA", "split", lambda s: s != "f32")
 # the fused FU's pass 1 reads pass 0's mix output instead of recomputing it (FFC_FU_SPILL=0: recompute)
-FU_SPILL = __import__("os").environ.get("FFC_FU_SPILL", "1") != "0"
+FU_SPILL = _env("FFC_FU_SPILL", "1", _not0)
 
 
 class BnFoldDesc:
@@ -376,7 +387,7 @@ def bn_fold(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, dev
 
 # SyncBN: reduce + all-reduce the moments, then finalize inside the consumer (ffc_bn_fold.moments)
 # instead of a separate ffc_bn_finalize launch (FFC_BN_FOLD_SYNC=0: the old path, A/B)
-BN_FOLD_SYNC = __import__("os").environ.get("FFC_BN_FOLD_SYNC", "1") != "0"
+BN_FOLD_SYNC = _env("FFC_BN_FOLD_SYNC", "1", _not0)
 
 
 # Per-channel in-kernel folds (ffc::bn_fold_channels): consumers whose workgroups / waves need only
@@ -388,13 +399,13 @@ BN_FOLD_SYNC = __import__("os").environ.get("FFC_BN_FOLD_SYNC", "1") != "0"
 # ffc_fu2d_r2c_mix was reproduced non-deterministic in round 6 (T of whole channels
 # wrong in co-resident workgroups, 39 of 40 repeated forwards) and its mechanism is not isolated, so
 # the single-rank path finalizes these BNs by their own launch (B = 32: +3 %, B = 256: neutral, r05c)
-BN_CHFOLD = __import__("os").environ.get("FFC_BN_CHFOLD", "0") == "1"
-BN_CHFOLD_LOADS = int(__import__("os").environ.get("FFC_BN_CHFOLD_LOADS", "16"))
-BN_CHFOLD_READS = int(__import__("os").environ.get("FFC_BN_CHFOLD_READS", "16384"))
+BN_CHFOLD = _env("FFC_BN_CHFOLD", "0", lambda s: s == "1")
+BN_CHFOLD_LOADS = _env("FFC_BN_CHFOLD_LOADS", "16", int)
+BN_CHFOLD_READS = _env("FFC_BN_CHFOLD_READS", "16384", int)
 # mirrors fu_kernels.hip fu_split_on(): FFC_FU_SPLIT=0 runs the fused FU's pass 1 as one workgroup per
 # sample, which folds a mix BN over its whole slab (bn_fold_block) -- a channel-only fold descriptor
 # (the split pass 1's) must not reach it
-FU_SPLIT = __import__("os").environ.get("FFC_FU_SPLIT", "1")[:1] != "0"
+FU_SPLIT = _env("FFC_FU_SPLIT", "1", lambda s: s[:1] != "0")
 # fused FU pass 0 over two bin groups per sample where the library takes them (ffc_fu_kgroups, round
 # 6; off unless FFC_FU_KGROUPS=2, which the library reads too -- measured neutral to slower);
 # FU_KGROUPS = False keeps one workgroup per sample even then
@@ -666,13 +677,20 @@ class PackCache:
 # --------------------------------------------------------------------------- convolution jobs
 
 
+# The module-level switches plans and templates depend on, by name: every switch of this module, with
+# or without an environment variable (tests/test_knobs_cpu.py checks that none is missing).
+PLAN_KNOBS = ("USE_PATCH", "PW_KERNEL", "CONV_ARITH", "PRESPLIT_A", "USE_CONVQ", "CONVQ_FORCE", "USE_OUTER",
+              "USE_SMALLM", "FORCE_FU2D", "FU_PATH", "FU_FUSED_MIN_BATCH", "FU_COLS", "FU2D_SPILL", "OVERLAP_SPECTRAL",
+              "BN_FOLD", "BN_FOLD_MAX", "FU_SPILL", "ST_PATH", "ST_SPLIT", "ST_SPLIT_MAX", "SE_SUMS", "BN_CHFOLD",
+              "BN_CHFOLD_LOADS", "BN_CHFOLD_READS", "ST_SPLIT_MFMA", "FU2D_R2CMIX", "FU_SPLIT", "FU_KGROUPS",
+              "BN_FOLD_SYNC")
+
+
 def plan_knobs():
-    """the module-level switches plans depend on (tests and A/B runs flip them): part of every plan
-    cache key, so a changed switch never meets a plan made under another setting"""
-    return (USE_PATCH, PW_KERNEL, CONV_ARITH, PRESPLIT_A, USE_CONVQ, CONVQ_FORCE, USE_OUTER, USE_SMALLM, FORCE_FU2D,
-            FU_PATH, FU_FUSED_MIN_BATCH, FU_COLS, FU2D_SPILL, OVERLAP_SPECTRAL, BN_FOLD, BN_FOLD_MAX, FU_SPILL, ST_PATH,
-            ST_SPLIT, ST_SPLIT_MAX, SE_SUMS, BN_CHFOLD, BN_CHFOLD_LOADS, BN_CHFOLD_READS, ST_SPLIT_MFMA, FU2D_R2CMIX,
-            FU_SPLIT, _plan.CONVQ_TCMAX, FU_KGROUPS, BN_FOLD_SYNC)
+    """the current values of PLAN_KNOBS and _plan.CONVQ_TCMAX (tests and A/B runs flip them): part of every
+    plan cache key, so a changed switch never meets a plan made under another setting"""
+    g = globals()
+    return tuple(g[n] for n in PLAN_KNOBS) + (_plan.CONVQ_TCMAX,)
 
 
 def algorithmic_flops(plan) -> float:
@@ -701,7 +719,7 @@ def algorithmic_flops(plan) -> float:
 USE_PATCH = True   # LDS-patch kernel where it applies (tests flip this to cover the generic kernel)
 # 1x1-only jobs of the training path: "pw" = ffc_pw_forward (tiled GEMM), "patch" / "gemm" = the
 # conv kernels (A/B measurements, tests)
-PW_KERNEL = __import__("os").environ.get("FFC_PW_KERNEL", "pw")
+PW_KERNEL = _env("FFC_PW_KERNEL", "pw")
 
 
 def pick_pw_cfg(B, M, Q):
@@ -713,41 +731,39 @@ def pick_pw_cfg(B, M, Q):
     return 2
 # LDS-patch conv products: "split" = fp32-accurate split-bf16 MFMA (three exact bf16 pieces per
 # operand, six piece products), "f32" = v_mfma_f32_32x32x2_f32 (A/B measurements, tests)
-CONV_ARITH = __import__("os").environ.get("FFC_CONV_ARITH", "split")
-PRESPLIT_A = __import__("os").environ.get("FFC_CONVP_PRESPLIT", "0") == "1"   # A/B knob: A3 planes (off: measured neutral / -1 %)
+CONV_ARITH = _env("FFC_CONV_ARITH", "split")
+PRESPLIT_A = _env("FFC_CONVP_PRESPLIT", "0", lambda s: s == "1")   # A/B knob: A3 planes (off: measured neutral / -1 %)
 # stride-2 transposed-conv jobs on ffc_convq_forward (operands split once while staged, warp-specialised,
 # persistent workgroups) under the split-bf16 products: taken wherever it plans ("auto" / "1" / "force");
 # "0" never (convp for everything, A/B measurements).  Until r02 it lost to convp on large grids; the
 # persistent grid (r03) reversed that (tools/convq_probe.py)
-USE_CONVQ = __import__("os").environ.get("FFC_CONVQ", "auto") != "0"
-CONVQ_FORCE = __import__("os").environ.get("FFC_CONVQ", "auto") in ("1", "force")
+USE_CONVQ = _env("FFC_CONVQ", "auto", _not0)
+CONVQ_FORCE = _env("FFC_CONVQ", "auto", lambda s: s in ("1", "force"))
 USE_OUTER = True   # ConvT on a 1x1 input as one outer-product GEMM (ffc._FFCExec._outer_rewrite)
 USE_SMALLM = True  # direct VALU ConvT for <= 4 output channels (ffc_convt_k4s2_smallm)
 FORCE_FU2D = False  # large-plane FU stages even where the fused per-sample FU applies (tests)
 # SpectralTransform prologue: "auto" = the fused per-sample kernel where the sample fits in LDS
 # (st_prologue.hip), else SE gate + gated 1x1 GEMM (st_pw.hip); "pw" forces the latter (A/B runs)
-ST_PATH = __import__("os").environ.get("FFC_ST_PATH", "auto")
+ST_PATH = _env("FFC_ST_PATH", "auto")
 # Fourier-unit path where both apply: the fused one-workgroup-per-sample kernel fills the chip only
 # with B >= ~CUs/4 samples; smaller batches run the staged kernels, which spread every sample over
 # many workgroups.  "auto" | "fused" | "staged".  The threshold was 128 until the fused mix ran on
 # pre-split weights (r05ad); gen64 B = 64 then measured 0.2161 -> 0.2147 ms fused (r05af)
-FU_PATH = __import__("os").environ.get("FFC_FU_PATH", "auto")
+FU_PATH = _env("FFC_FU_PATH", "auto")
 FU_FUSED_MIN_BATCH = 64
 FU_COLS = True      # staged FU: inverse column FFT fused into mix pass 1, rows-only C2R (H in 32..128)
 # staged FU, batch-statistics BN: pass 0 spills the raw Y and the whole-plane C2R applies BN + ReLU on
 # load (no second mix); FFC_FU2D_SPILL=0 keeps the two-pass mix
-FU2D_SPILL = __import__("os").environ.get("FFC_FU2D_SPILL", "1") != "0"
+FU2D_SPILL = _env("FFC_FU2D_SPILL", "1", _not0)
 # staged FU with the spill on small t planes (h in {8, 16}, C in {16, 32}): the R2C inside mix pass 0
 # (ffc_fu2d_r2c_mix: one launch instead of two); FFC_FU2D_R2CMIX=0 keeps the separate R2C
-FU2D_R2CMIX = __import__("os").environ.get("FFC_FU2D_R2CMIX", "1") != "0"
+FU2D_R2CMIX = _env("FFC_FU2D_R2CMIX", "1", _not0)
 # Run SpectralTransform's kernels on a side stream beside the local-branch GEMM of the same FFC
 # layer ("gemm-first" / "spectral-first": which is issued first).  Off by default: measured on
 # MI355X (B=256 generator) 10-18 % slower than one launch pairing the local and global GEMMs,
 # because the FU / ST kernels' LDS footprint cannot co-reside with the GEMM workgroups and the
 # separate GEMM launches lose the heavy/light tile pairing.
-OVERLAP_SPECTRAL = __import__("os").environ.get("FFC_OVERLAP", "off")
-if OVERLAP_SPECTRAL in ("0", "off", "false"):
-    OVERLAP_SPECTRAL = False
+OVERLAP_SPECTRAL = _env("FFC_OVERLAP", "off", lambda s: False if s in ("0", "off", "false") else s)
 
 _SIDE = {}
 

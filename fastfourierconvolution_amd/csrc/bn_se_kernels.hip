@@ -8,8 +8,6 @@
 #include "bn_common.h"
 
 #include <algorithm>
-#include <cstdlib>
-
 #include <cmath>
 
 namespace {
@@ -325,10 +323,7 @@ __global__ void se_fc_kernel(const float* means, int C, const float* __restrict_
 // S partials of a channel in a fixed order (lane-strided sums, one shuffle tree) and finalizes.
 constexpr int RED2_MIN_ROWS = 1024;   // FFC_BN_RED2_MIN overrides (A/B runs)
 int red2_min_rows() {
-    static const int v = [] {
-        const char* e = std::getenv("FFC_BN_RED2_MIN");
-        return e && *e ? std::max(1, std::atoi(e)) : RED2_MIN_ROWS;
-    }();
+    static const int v = std::max(1, ffc::env_int("FFC_BN_RED2_MIN", RED2_MIN_ROWS));
     return v;
 }
 

@@ -1,7 +1,10 @@
-// C-ABI plumbing: thread-local error text and launch checks.
+// C-ABI plumbing: thread-local error text, launch checks, the launch-support helpers.
 #include <hip/hip_runtime.h>
 
+#include <mutex>
+#include <set>
 #include <string>
+#include <utility>
 
 #include "ffc_internal.h"
 
@@ -18,6 +21,31 @@ int launch_status(const char* what) {
         return FFC_E_LAUNCH;
     }
     return FFC_OK;
+}
+
+int raise_dynamic_lds(const void* kernel, size_t lds_bytes, const char* what) {
+    if (lds_bytes <= 64 * 1024) return FFC_OK;
+    static std::mutex mu;
+    static std::set<std::pair<const void*, int>> raised;
+    std::lock_guard<std::mutex> g(mu);
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e == hipSuccess && raised.count({kernel, dev})) return FFC_OK;
+    if (e == hipSuccess) e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e != hipSuccess) {
+        set_error(std::string(what) + ": hipFuncSetAttribute: " + hipGetErrorString(e));
+        return FFC_E_LAUNCH;
+    }
+    raised.insert({kernel, dev});
+    return FFC_OK;
+}
+
+int cu_count() {
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+        return 0;
+    return cus;
 }
 
 }  // namespace ffc

@@ -492,18 +492,7 @@ __global__ __launch_bounds__(256) void convp_kernel(ConvPArgs args_byval) {
 template <int NP, int NTW, int AR>
 int launch(const ConvPArgs& a, int ntiles, size_t lds, hipStream_t s) {
     auto k = convp_kernel<NP, NTW, AR>;
-    if (lds > 64 * 1024) {
-        static bool raised = false;  // per instantiation
-        if (!raised) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) {
-                ffc::set_error(std::string("ffc_convp_forward: hipFuncSetAttribute: ") + hipGetErrorString(e));
-                return FFC_E_LAUNCH;
-            }
-            raised = true;
-        }
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_convp_forward")) return rc;
     hipLaunchKernelGGL(k, dim3(ntiles), dim3(256), lds, s, a);
     return ffc::launch_status("ffc_convp_forward");
 }

@@ -32,7 +32,6 @@
 #include "ffc_internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <map>
 #include <mutex>
 #include <string>
@@ -837,10 +836,7 @@ __global__ __launch_bounds__(256) void convq_reduce_kernel(ConvQArgs args_byval,
 // count: workgroup b then stays on XCD b % 8 for all its tiles), never more than the tiles.
 // FFC_CONVQ_PERSIST=0 launches one workgroup per tile (the previous grid; A/B measurements).
 int persistent_grid(const void* k, size_t lds, int ntiles) {
-    static const bool off = [] {
-        const char* e = getenv("FFC_CONVQ_PERSIST");
-        return e && e[0] == '0';
-    }();
+    static const bool off = ffc::env_first("FFC_CONVQ_PERSIST") == '0';
     if (off) return ntiles;
     static std::mutex mu;
     static std::map<std::tuple<const void*, size_t, int>, int> cache;
@@ -856,9 +852,9 @@ int persistent_grid(const void* k, size_t lds, int ntiles) {
         if (it != cache.end()) {
             slots = it->second;
         } else {
-            int cus = 0, per = 0;
-            if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-                hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, QTHREADS, lds) != hipSuccess || cus <= 0) {
+            const int cus = ffc::cu_count();
+            int per = 0;
+            if (cus <= 0 || hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, k, QTHREADS, lds) != hipSuccess) {
                 ffc::set_error("ffc_convq_forward: occupancy query failed");
                 return -1;
             }
@@ -873,18 +869,7 @@ int persistent_grid(const void* k, size_t lds, int ntiles) {
 template <int MT, int NTW, int SL = QSLOTS, int PX = 4>
 int launch_q(const ConvQArgs& a, int ntiles, size_t lds, hipStream_t s, const int4* slots, int nslots) {
     auto k = convq_kernel<MT, NTW, SL, PX>;
-    if (lds > 64 * 1024) {
-        static bool raised = false;   // per instantiation
-        if (!raised) {
-            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) {
-                ffc::set_error(std::string("ffc_convq_forward: hipFuncSetAttribute: ") + hipGetErrorString(e));
-                return FFC_E_LAUNCH;
-            }
-            raised = true;
-        }
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_convq_forward")) return rc;
     const int grid = persistent_grid(reinterpret_cast<const void*>(k), lds, ntiles);
     if (grid <= 0) return FFC_E_LAUNCH;
     hipLaunchKernelGGL(k, dim3(grid), dim3(QTHREADS), lds, s, a);
@@ -898,21 +883,14 @@ int launch_q(const ConvQArgs& a, int ntiles, size_t lds, hipStream_t s, const in
 }
 
 int stage_px(int units4) {
-    static const int force = [] {
-        const char* e = getenv("FFC_CONVQ_PX");
-        return e ? atoi(e) : 0;
-    }();
+    static const int force = ffc::env_int("FFC_CONVQ_PX", 0);
     const int fit = 4 * units4 <= 256 ? 1 : (2 * units4 <= 256 ? 2 : 4);   // one unit per staging thread
     return (force == 1 || force == 2 || force == 4) && force >= fit ? force : fit;
 }
 
 int slots11() {
-    static const int v = [] {
-        const char* e = getenv("FFC_CONVQ_SLOTS11");
-        const int n = e ? atoi(e) : 0;
-        return (n == 3 || n == 4) ? n : QSLOTS;
-    }();
-    return v;
+    static const int n = ffc::env_int("FFC_CONVQ_SLOTS11", 0);
+    return (n == 3 || n == 4) ? n : QSLOTS;
 }
 
 }  // namespace

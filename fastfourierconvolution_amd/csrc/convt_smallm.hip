@@ -24,7 +24,6 @@
 #include "ffc_internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace {
 
@@ -750,15 +749,7 @@ extern "C" int ffc_convt_k4s2_smallm(const float* x0, int C0, const float* x1, i
           convt_smallm_kernel<4, true, 8, 8>}}};
     const int vec = IW % 4 == 0 ? 1 : 0;
     auto k = kernels[small][vec][M - 1];
-    static bool raised[2][2][5] = {};
-    if (!raised[small][vec][M]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) {
-            ffc::set_error("ffc_convt_k4s2_smallm: hipFuncSetAttribute failed");
-            return FFC_E_LAUNCH;
-        }
-        raised[small][vec][M] = true;
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_convt_k4s2_smallm")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3((CT_TT / 2) * (tr / 2) * nq), lds, (hipStream_t)stream, a);
     return ffc::launch_status("ffc_convt_k4s2_smallm");
 }
@@ -789,10 +780,7 @@ static int conv3x3_smallm_launch(const float* x0, int C0, const float* w0, const
     a.M = M;
     // tile rows: 32 (two workgroups per CU; measured: fgan128 B = 512 head 2.25 -> 2.11 ms, B = 64 neutral,
     // profiles/r02/s15); FFC_HEAD_TR=64 restores the full-height tile for A/B runs
-    static const int tr = [] {
-        const char* e = std::getenv("FFC_HEAD_TR");
-        return e && std::atoi(e) == 64 ? 64 : 32;
-    }();
+    static const int tr = ffc::env_int("FFC_HEAD_TR", 32) == 64 ? 64 : 32;
     a.nty = (H + tr - 1) / tr;
     a.ntx = (W + T3 - 1) / T3;
     a.act = act;
@@ -825,15 +813,7 @@ static int conv3x3_smallm_launch(const float* x0, int C0, const float* w0, const
           conv3x3_smallm_kernel<4, true, 32>}}};
     const int ti = tr == 32 ? 1 : 0;
     auto k = kernels[ti][tf ? 1 : 0][M - 1];
-    static bool raised[2][2][5] = {};
-    if (!raised[ti][tf][M]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                160 * 1024) != hipSuccess) {
-            ffc::set_error("ffc_conv3x3_smallm: hipFuncSetAttribute failed");
-            return FFC_E_LAUNCH;
-        }
-        raised[ti][tf][M] = true;
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_conv3x3_smallm")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3(tr == 32 ? 2 * Head3<32>::HT : 2 * Head3<64>::HT), lds,
                        (hipStream_t)stream, a);
     return ffc::launch_status("ffc_conv3x3_smallm");

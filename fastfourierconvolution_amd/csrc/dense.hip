@@ -8,8 +8,6 @@
 // Workgroup tile: 64 rows (b) x 64 columns (n), A staged in LDS; each of the 4 waves owns 32 x 32.
 #include "ffc_internal.h"
 
-#include <cstdlib>
-
 namespace {
 
 constexpr int DN_THREADS = 256;
@@ -164,10 +162,7 @@ extern "C" int ffc_dense_forward(const float* A, const float* Wt, const float* b
     DenseArgs a{A, Wt, bias, out0, out1, B, K, N, N0, act, act_param};
     const int grid = ((B + DN_BM - 1) / DN_BM) * ((N + DN_BN - 1) / DN_BN);
     const int KH = K <= 128 ? 64 : 128;
-    static const bool vec_on = [] {   // FFC_DENSE_VEC=0: the scalar-load staging (A/B)
-        const char* e = std::getenv("FFC_DENSE_VEC");
-        return !(e && e[0] == '0');
-    }();
+    static const bool vec_on = ffc::env_first("FFC_DENSE_VEC") != '0';   // =0: the scalar-load staging (A/B)
     const bool vec = vec_on && K % 4 == 0 && N % 4 == 0 && (reinterpret_cast<uintptr_t>(A) & 15) == 0 &&
                      (reinterpret_cast<uintptr_t>(Wt) & 15) == 0;
     const size_t lds = sizeof(float) * (DN_BM * (2 * KH + 1) + (vec ? 2 * KH * 64 : 0));
@@ -175,17 +170,7 @@ extern "C" int ffc_dense_forward(const float* A, const float* Wt, const float* b
     static const DenseKernel kernels[2][2] = {{dense_kernel<64, false>, dense_kernel<64, true>},
                                               {dense_kernel<128, false>, dense_kernel<128, true>}};
     const DenseKernel k = kernels[KH == 128][vec];
-    if (lds > 64 * 1024) {
-        static bool raised[2][2] = {};
-        if (!raised[KH == 128][vec]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess) {
-                ffc::set_error("ffc_dense_forward: hipFuncSetAttribute failed");
-                return FFC_E_LAUNCH;
-            }
-            raised[KH == 128][vec] = true;
-        }
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_dense_forward")) return rc;
     hipLaunchKernelGGL(k, dim3(grid), dim3(DN_THREADS), lds, (hipStream_t)stream, a);
     return ffc::launch_status("ffc_dense_forward");
 }

@@ -5,6 +5,7 @@
 #include <string>
 
 #include "../../include/ffc_amd.h"
+#include "ffc_env.h"   // ffc::env_int / env_first / env_is
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 typedef float floatx4 __attribute__((ext_vector_type(4)));
@@ -108,6 +109,17 @@ __device__ __forceinline__ floatx4 buf_ld4(__amdgpu_buffer_rsrc_t r, unsigned of
 
 void set_error(const std::string& msg);
 int launch_status(const char* what);  // FFC_OK or FFC_E_LAUNCH after checking hipGetLastError
+// Opt `kernel` into 160 KiB of dynamic LDS before a launch that asks for more than 64 KiB (no-op at
+// or below): once per (kernel, current device) under one mutex -- a kernel is loaded per device, and
+// nothing documents the attribute as shared between devices.  Not a stream operation, so legal
+// under graph capture.  FFC_OK, or FFC_E_LAUNCH with the error text set ("<what>: ..." and the HIP
+// error string).
+int raise_dynamic_lds(const void* kernel, size_t lds_bytes, const char* what);
+template <class K>
+int raise_dynamic_lds(K* kernel, size_t lds_bytes, const char* what) {
+    return raise_dynamic_lds(reinterpret_cast<const void*>(kernel), lds_bytes, what);
+}
+int cu_count();  // compute units of the current device; <= 0 when the query fails
 // the training path's planar 2-D real transforms on the fu2d line FFTs (fu2d_kernels.hip): square
 // power-of-two planes up to 128; return 1 when the plane is not handled there (direct DFT instead)
 int fft_planes_r2c(const float* x, int P, int H, int W, float iscale, float* Z, void* stream);

@@ -26,10 +26,7 @@
 #include "ffc_internal.h"
 
 #include <algorithm>
-#include <cstdlib>
 #include <cmath>
-#include <mutex>
-#include <set>
 
 #include "fft_common.h"
 #include "bn_common.h"
@@ -1530,30 +1527,11 @@ size_t mix_lds(int C, int pass, bool f16 = false) {
     return 4 * (wm + tail);
 }
 
-int raise_lds(const void* k, size_t lds, const char* what) {
-    if (lds <= 64 * 1024) return FFC_OK;
-    static std::mutex mu;
-    static std::set<const void*> raised;
-    std::lock_guard<std::mutex> g(mu);
-    if (raised.count(k)) return FFC_OK;
-    hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) {
-        ffc::set_error(std::string(what) + ": hipFuncSetAttribute: " + hipGetErrorString(e));
-        return FFC_E_LAUNCH;
-    }
-    raised.insert(k);
-    return FFC_OK;
-}
-
 // workgroups per sample: ~MIX_TILES_PER_WG bin tiles each (2 per wave), but enough workgroups
 // (>= ~1024) to fill the chip when the batch is small, down to one tile per workgroup
 int mix_fill_target() {   // FFC_MIX_FILL: workgroups the split aims for at small batches (A/B)
-    static const int v = [] {
-        const char* e = std::getenv("FFC_MIX_FILL");
-        const int n = e ? std::atoi(e) : 0;
-        return n > 0 ? n : 512;
-    }();
-    return v;
+    static const int n = ffc::env_int("FFC_MIX_FILL", 0);
+    return n > 0 ? n : 512;
 }
 int mix_nsplit(int B, int H, int W) {
     const int ntiles = (H * (W / 2 + 1) + 31) / 32;
@@ -1601,7 +1579,7 @@ extern "C" int ffc_fu2d_r2c_ex(const float* t, int B, int C, int h, int w, const
     FFC_CHECK_ARG(k != nullptr, "ffc_fu2d_r2c: unsupported plane (square, power of two in [8, 128])");
     const size_t lds = r2c_lds(h, w);
     FFC_CHECK_ARG(lds <= 160 * 1024, "ffc_fu2d_r2c: plane exceeds LDS");
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_fu2d_r2c");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu2d_r2c");
     if (rc) return rc;
     R2cArgs a{t, in_scale, in_shift, T, C, in_relu, 1.0f, 1.0f};
     a.has_fold = in_fold != nullptr;
@@ -1638,7 +1616,7 @@ extern "C" int ffc_fu2d_mix(const float* T, int B, int C, int H, int W, int up, 
     a.Mpad = (2 * C + 31) / 32 * 32;
     a.norm = (float)(1.0 / std::sqrt((double)H * (double)W));
     const size_t lds = mix_lds(C, pass);
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_fu2d_mix");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu2d_mix");
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(B * a.nsplit), dim3(FU2_THREADS), lds, (hipStream_t)stream, a);
     return ffc::launch_status("ffc_fu2d_mix");
@@ -1692,7 +1670,7 @@ extern "C" int ffc_fu2d_r2c_mix(const float* t, int B, int C, int H, int W, int 
 #ifdef FFC_R2CMIX_FRONTPAD
     lds += FFC_R2CMIX_FRONTPAD;
 #endif
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_fu2d_r2c_mix");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu2d_r2c_mix");
     if (rc) return rc;
     R2cMixArgs ra;
     MixArgs& a = ra.m;
@@ -1779,7 +1757,7 @@ static int fu2d_c2r_launch(const float* Y, int B, int C, int H, int W, const flo
     C2rKernel k = pick_c2r(H, W, up);
     FFC_CHECK_ARG(k != nullptr, "ffc_fu2d_c2r: unsupported plane (square, power of two in [16, 128])");
     const size_t lds = c2r_lds(H, W);
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_fu2d_c2r");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu2d_c2r");
     if (rc) return rc;
     hipLaunchKernelGGL(k, dim3(B * C), dim3(FU2_THREADS), lds, (hipStream_t)stream, a);
     return ffc::launch_status("ffc_fu2d_c2r");
@@ -1835,7 +1813,7 @@ extern "C" int ffc_fu2d_mix_cols(const float* T, int B, int C, int H, int W, int
     a.Mpad = (2 * C + 31) / 32 * 32;
     a.norm = (float)(1.0 / std::sqrt((double)H * (double)W));
     const size_t lds = cols_lds(C, f16);
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_fu2d_mix_cols");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu2d_mix_cols");
     if (rc) return rc;
     const int cpw = 4 / (H / 32);
     const int ncg = (W / 2 + 1 + cpw - 1) / cpw;
@@ -1896,7 +1874,7 @@ int fft_planes_r2c(const float* x, int P, int H, int W, float iscale, float* Z, 
     if (!k) return 1;
     const size_t lds = r2c_lds(H, W);
     if (lds > 160 * 1024) return 1;
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_rfft2_planes");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_rfft2_planes");
     if (rc) return rc;
     R2cArgs a{x, nullptr, nullptr, Z, 1, 0, (float)(1.0 / std::sqrt((double)H * (double)W)), iscale};
     hipLaunchKernelGGL(k, dim3(P), dim3(FU2_THREADS), lds, (hipStream_t)stream, a);
@@ -1908,7 +1886,7 @@ int fft_planes_c2r(const float* Z, int P, int H, int W, float iscale, const floa
     if (!k) return 1;
     const size_t lds = c2r_lds(H, W);
     if (lds > 160 * 1024) return 1;
-    int rc = raise_lds(reinterpret_cast<const void*>(k), lds, "ffc_irfft2_planes");
+    int rc = ffc::raise_dynamic_lds(k, lds, "ffc_irfft2_planes");
     if (rc) return rc;
     C2rArgs a{Z, addend, nullptr, nullptr, y, 1, 0, addend ? 1 : 0,
               (float)(1.0 / std::sqrt((double)H * (double)W)), nullptr, nullptr, iscale};

@@ -18,9 +18,6 @@
 #include "bn_common.h"
 
 #include <cmath>
-#include <cstdlib>
-#include <mutex>
-#include <set>
 
 #include "fft_common.h"
 
@@ -907,49 +904,32 @@ KgLayout kg_layout(int C, int H, int W, int G, bool wm) {
 }
 // FFC_FU_KGROUPS: 2 = on, anything else off (fu_kernel's pass 0, one workgroup or M-tile groups per sample)
 int fu_kgroups_env() {
-    static const int v = [] {
-        const char* e = std::getenv("FFC_FU_KGROUPS");
-        return e ? std::atoi(e) : -1;
-    }();
+    static const int v = ffc::env_int("FFC_FU_KGROUPS", -1);
     return v;
 }
 
 // FFC_FU_MFMA=split: the fused mix on the split-bf16 products instead of the exact f32-input MFMA.
 // Off by default: measured neutral (gen64 B = 256 fu_pass0 51 vs 52 us per step, B = 32 the same,
 // r05f) -- the fused mix waits on its LDS operand reads and the per-tile statistics, not the MFMA
-bool fu_mix3_on() {
-    static const bool on = [] {
-        const char* e = std::getenv("FFC_FU_MFMA");
-        return e && e[0] == 's';
-    }();
-    return on;
+char fu_mfma_env() {
+    static const char c = ffc::env_first("FFC_FU_MFMA");
+    return c;
 }
+bool fu_mix3_on() { return fu_mfma_env() == 's'; }
 // with pre-split weights (ffc_fu_forward_ex3) the split mix is the default; FFC_FU_MFMA=f32 keeps the
 // exact f32-input MFMA (A/B)
-bool fu_mix_f32_forced() {
-    static const bool on = [] {
-        const char* e = std::getenv("FFC_FU_MFMA");
-        return e && e[0] == 'f';
-    }();
-    return on;
-}
+bool fu_mix_f32_forced() { return fu_mfma_env() == 'f'; }
 // FFC_FU_SHUF=1: the column DFTs across lanes (fft_common.h lane_fft_dif / lane_ifft_dit) instead of
 // through LDS (one lane per column line).  Off by default: measured level with the LDS column pass at
 // gen64 B = 256 and B = 32 (round 6) -- the row / column phases are VALU-issue bound, and
 // the lane form spends in butterfly arithmetic on every lane what it saves in LDS traffic and barriers
 bool fu_shuf_on() {
-    static const bool on = [] {
-        const char* e = std::getenv("FFC_FU_SHUF");
-        return e && e[0] == '1';
-    }();
+    static const bool on = ffc::env_first("FFC_FU_SHUF") == '1';
     return on;
 }
 // FFC_FU_SPLIT=0: pass 1 as one workgroup per sample (fu_kernel) for A/B runs
 bool fu_split_on() {
-    static const bool on = [] {
-        const char* e = std::getenv("FFC_FU_SPLIT");
-        return !(e && e[0] == '0');
-    }();
+    static const bool on = ffc::env_first("FFC_FU_SPLIT") != '0';
     return on;
 }
 
@@ -1181,33 +1161,15 @@ static int fu_forward_impl(const float* t, int B, int C, int H, int W, int up, c
         a.w3_lds = kl.wm_lds;
         a.scr_off = kl.scr_off;
         a.bn_off = kl.bn_off;
-        if (kl.bytes > 64 * 1024) {
-            static std::mutex mu;
-            static std::set<const void*> raised;
-            std::lock_guard<std::mutex> g(mu);
-            if (!raised.count(reinterpret_cast<const void*>(kk))) {
-                hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kk),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                if (e != hipSuccess) {
-                    ffc::set_error(std::string("ffc_fu_forward: hipFuncSetAttribute: ") + hipGetErrorString(e));
-                    return FFC_E_LAUNCH;
-                }
-                raised.insert(reinterpret_cast<const void*>(kk));
-            }
-        }
+        if (int rc = ffc::raise_dynamic_lds(kk, kl.bytes, "ffc_fu_forward")) return rc;
         hipLaunchKernelGGL(kk, dim3((unsigned)B * 2), dim3(FU_THREADS), kl.bytes, (hipStream_t)stream, a);
         return ffc::launch_status("ffc_fu_forward");
     }
     if (pass == 0) {
-        static const int force = [] {
-            const char* e = std::getenv("FFC_FU_MGROUPS");
-            return e ? std::atoi(e) : 0;
-        }();
+        static const int force = ffc::env_int("FFC_FU_MGROUPS", 0);
         const int MT = (2 * C + 31) / 32;
-        int cus = 256, dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
-            cus = 256;
+        int cus = ffc::cu_count();
+        if (cus <= 0) cus = 256;
         for (int g : {4, 2}) {   // 2 unless forced: 4 groups repeat the FFTs once too often (B = 32: r05an)
             if (force <= 0 && g == 4) continue;
             if (force > 0 ? g == force : (long long)B * g <= cus) {
@@ -1218,21 +1180,7 @@ static int fu_forward_impl(const float* t, int B, int C, int H, int W, int up, c
             }
         }
     }
-    if (lds > 64 * 1024) {
-        // opt each instance into the full 160 KiB once (not a stream op; safe under capture)
-        static std::mutex mu;
-        static std::set<const void*> raised;
-        std::lock_guard<std::mutex> g(mu);
-        if (!raised.count(reinterpret_cast<const void*>(k))) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) {
-                ffc::set_error(std::string("ffc_fu_forward: hipFuncSetAttribute: ") + hipGetErrorString(e));
-                return FFC_E_LAUNCH;
-            }
-            raised.insert(reinterpret_cast<const void*>(k));
-        }
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu_forward")) return rc;
     // pass 1 from the spill with the BN scale / shift given, or a mix fold the waves can take channel by
     // channel (momentum >= 0: ffc::bn_fold_channels): one wave per (sample, 64 / H channels)
     const bool chan_fold = mix_fold && mix_fold->momentum >= 0.0f && (2 * 64 / H) <= 64;

@@ -10,8 +10,6 @@
 // v_mfma_f32_32x32x2_f32 with the gate folded into the B-fragment read.
 #include "ffc_internal.h"
 
-#include <mutex>
-#include <set>
 #include <string>
 
 namespace {
@@ -480,18 +478,7 @@ extern "C" int ffc_st_prologue_ex3(const float* x, int B, int Cin, int H, int W,
                   "ffc_st_prologue: sample does not fit in LDS (use se_gate + conv)");
     const StLayout L = st_layout(Cin, H, W, pool, hidden, c, wc3 == nullptr);
     const size_t lds = L.bytes;
-    if (lds > 64 * 1024) {
-        static std::once_flag once;
-        static hipError_t err = hipSuccess;
-        std::call_once(once, [] {
-            err = hipFuncSetAttribute(reinterpret_cast<const void*>(st_prologue_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        });
-        if (err != hipSuccess) {
-            ffc::set_error(std::string("ffc_st_prologue: hipFuncSetAttribute: ") + hipGetErrorString(err));
-            return FFC_E_LAUNCH;
-        }
-    }
+    if (int rc = ffc::raise_dynamic_lds(st_prologue_kernel, lds, "ffc_st_prologue")) return rc;
     StArgs a;
     a.x = x;
     a.w1 = w1;

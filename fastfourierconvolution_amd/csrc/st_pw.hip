@@ -168,18 +168,7 @@ extern "C" int ffc_pw_gate_conv(const float* x, const float* gate, const float* 
     a.nblk = ffc_pw_gate_blocks(HW);
     a.Mpad = (M + 31) / 32 * 32;
     PwKernel k = a.Mpad <= 32 ? pw_gate_kernel<1> : a.Mpad <= 64 ? pw_gate_kernel<2> : pw_gate_kernel<4>;
-    if (lds > 64 * 1024) {
-        static bool raised[3] = {false, false, false};
-        const int i = a.Mpad <= 32 ? 0 : a.Mpad <= 64 ? 1 : 2;
-        if (!raised[i]) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    160 * 1024) != hipSuccess) {
-                ffc::set_error("ffc_pw_gate_conv: hipFuncSetAttribute failed");
-                return FFC_E_LAUNCH;
-            }
-            raised[i] = true;
-        }
-    }
+    if (int rc = ffc::raise_dynamic_lds(k, lds, "ffc_pw_gate_conv")) return rc;
     hipLaunchKernelGGL(k, dim3((unsigned)(B * a.nblk)), dim3(PW_THREADS), lds, (hipStream_t)stream, a);
     return ffc::launch_status("ffc_pw_gate_conv");
 }

@@ -23,8 +23,6 @@
 
 #include "ffc_internal.h"
 
-#include <cstdlib>
-
 namespace {
 
 __device__ __forceinline__ float act_grad_from_out(float y, float x_or_y, int act, float p) {
@@ -977,17 +975,13 @@ extern "C" int ffc_conv_wgrad(const float* U, int Mu, int PH, int PW, const floa
     FFC_CHECK_ARG(a.out, "ffc_conv_wgrad: accumulate needs a workspace");
     const int bt = wgrad_tile(Mu, NT);
     dim3 grid((NT + bt - 1) / bt, (Mu + bt - 1) / bt, S);
-    static const int bk_knob = [] {   // A/B measurement knob (tools/wgrad_probe.py): K chunk depth
-        const char* e = getenv("FFC_WGRAD_BK");
-        return e ? atoi(e) : 0;
-    }();
-    static const bool exact = [] {    // A/B knob: f32-input MFMA instead of the split-bf16 products
-        const char* e = getenv("FFC_WGRAD_ARITH");
-        return e && std::string(e) == "f32";
-    }();
+    // A/B measurement knob (tools/wgrad_probe.py): K chunk depth
+    static const int bk_knob = ffc::env_int("FFC_WGRAD_BK", 0);
+    // A/B knob: f32-input MFMA instead of the split-bf16 products
+    static const bool exact = ffc::env_is("FFC_WGRAD_ARITH", "f32");
     auto go = [&](auto kern) { hipLaunchKernelGGL(kern, grid, dim3(256), 0, (hipStream_t)stream, a); };
-    const char* kv = getenv("FFC_WGRAD_KERNEL");   // A/B knob: "old" = the split-per-use kernel below
-    if (!exact && !bk_knob && !(kv && std::string(kv) == "old")) {
+    // A/B knob, read on every call: "old" = the split-per-use kernel below
+    if (!exact && !bk_knob && !ffc::env_is("FFC_WGRAD_KERNEL", "old")) {
         bt == 128 ? go(wgradq_kernel<128, 128>) : go(wgradq_kernel<64, 64>);
     } else if (bt == 128) {   // 32-deep chunks: 64 MFMAs per wave between barriers (measured 18 % faster than 16)
         if (bk_knob == 16)
