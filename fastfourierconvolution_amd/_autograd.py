@@ -19,6 +19,8 @@ no CPU fallback):
   rfftn + Re/Im interleave (fourier_unity.py:38-42)          ffc::rfft2         ffc::irfft2 (mirrored x 0.5)
   de-interleave + irfftn (+ x residual) (:51-56, ST :108)     ffc::irfft2        ffc::rfft2 (mirrored x 2)
   NoiseInjection (noise_injection.py:25-32)                  ffc::noise_inject  ffc::noise_wgrad
+  local Fourier unit's split / cat and repeat + add           ffc::lfu_split     ffc::lfu_split_backward
+    (spectral_transform.py:94-108; with set_lfu only)         ffc::lfu_tile_add  ffc::lfu_tile_backward
 
 FFT adjoints (verified in fp64): d/dX of irfftn(ortho) is rfftn(ortho) with the
 mirrored bins doubled; d/dx of rfftn(ortho) is irfftn(ortho) with the mirrored bins halved.
@@ -647,20 +649,80 @@ def fourier_unit(fu, x, residual: bool):
     return torch.ops.ffc.irfft2(R, H, W, 1.0, x if residual else None)
 
 
+# --------------------------------------------------------------------------- local Fourier unit (LFU)
+def _lfu_dims(x, what):
+    B, c, H, W = x.shape
+    if c % 4 or H % 2 or W % 2 or H < 2 or W < 2:
+        raise NotImplementedError(f"{what}: needs channels % 4 == 0 and even H, W; got {tuple(x.shape)}")
+    return B, c, H, W
+
+
+def lfu_split_impl(s):
+    """ffc::lfu_split: the quadrant stack xs (B, c, H/2, W/2) of the first c/4 channels of s (B, c, H, W);
+    channel blocks top-left, bottom-left, top-right, bottom-right (ffc_lfu_gather, identity transform)"""
+    s = rt.require(s, "s")
+    B, c, H, W = _lfu_dims(s, "lfu_split")
+    xs = torch.empty((B, c, H // 2, W // 2), device=s.device, dtype=torch.float32)
+    with rt.observe("lfu_gather", bytes=4.0 * (s.numel() // 4 + xs.numel())):
+        check(rt.lib().ffc_lfu_gather(ptr(s), B, c, H, W, 1, None, None, 0, ptr(xs), _stream(s)), "ffc_lfu_gather")
+    return xs
+
+
+def lfu_split_backward_impl(dxs):
+    """ffc::lfu_split_backward: ds (B, c, H, W) from dxs (B, c, H/2, W/2); zeros beyond channel c/4"""
+    dxs = rt.require(dxs, "dxs")
+    B, c, H2, W2 = dxs.shape
+    ds = torch.empty((B, c, 2 * H2, 2 * W2), device=dxs.device, dtype=torch.float32)
+    with rt.observe("lfu_gather_bwd", bytes=4.0 * (dxs.numel() + ds.numel())):
+        check(rt.lib().ffc_lfu_gather_bwd(ptr(dxs), B, c, 2 * H2, 2 * W2, ptr(ds), _stream(dxs)),
+              "ffc_lfu_gather_bwd")
+    return ds
+
+
+def lfu_tile_add_impl(v, ys, out=None):
+    """ffc::lfu_tile_add: v + ys.repeat(1, 1, 2, 2) (ffc_lfu_tile_add; out=v: in place)"""
+    v, ys = rt.require(v, "v"), rt.require(ys, "ys")
+    B, c, H, W = _lfu_dims(v, "lfu_tile_add")
+    if tuple(ys.shape) != (B, c, H // 2, W // 2):
+        raise RuntimeError(f"lfu_tile_add: ys must be {(B, c, H // 2, W // 2)}, got {tuple(ys.shape)}")
+    if out is None:
+        out = torch.empty_like(v)
+    with rt.observe("lfu_tile_add", bytes=4.0 * (2 * v.numel() + ys.numel())):
+        check(rt.lib().ffc_lfu_tile_add(ptr(v), ptr(ys), B, c, H, W, ptr(out), _stream(v)), "ffc_lfu_tile_add")
+    return out
+
+
+def lfu_tile_backward_impl(dv):
+    """ffc::lfu_tile_backward: dys (B, c, H/2, W/2) = the four quadrants of dv summed (fixed order)"""
+    dv = rt.require(dv, "dv")
+    B, c, H, W = _lfu_dims(dv, "lfu_tile_backward")
+    dys = torch.empty((B, c, H // 2, W // 2), device=dv.device, dtype=torch.float32)
+    with rt.observe("lfu_tile_bwd", bytes=4.0 * (dv.numel() + dys.numel())):
+        check(rt.lib().ffc_lfu_tile_bwd(ptr(dv), B, c, H, W, ptr(dys), _stream(dv)), "ffc_lfu_tile_bwd")
+    return dys
+
+
 def spectral_v(st, x):
-    """v = s + fu(s), s = relu(bn1(conv1(se(downsample(x))))) (spectral_transform.py:77-108, before conv2)"""
+    """v = s + fu(s) [+ tile(lfu(quadrants of s)) when st.run_lfu], s = relu(bn1(conv1(se(downsample(x)))))
+    (spectral_transform.py:77-108, before conv2)"""
     if st.groups != 1:
         raise NotImplementedError("grouped SpectralTransform (groups != 1) is not on the hot path")
     if st.stride == 2 and st.upsample:
         x = torch.ops.ffc.up2(x, 1.0)
     elif st.stride == 2:
         x = torch.ops.ffc.pool2(x, 0.25)
-    x = se_layer(st.se_block, x)
     B, Cin, H, W = x.shape
     c = st.conv1.out_channels
+    if st.run_lfu:
+        st.lfu_check(c, H, W)
+    x = se_layer(st.se_block, x)
     (t,) = conv_layer(B, [(c, 0, 0.0)], [(0, 0, _plan.Seg("pw", Cin, H, W), st.conv1)], [x])
     s = bn_act(st.bn1, t, (1, 0.0))
-    return fourier_unit(st.fu, s, residual=True)
+    v = fourier_unit(st.fu, s, residual=True)
+    if not st.run_lfu:
+        return v
+    ys = fourier_unit(st.lfu, torch.ops.ffc.lfu_split(s), residual=False)
+    return torch.ops.ffc.lfu_tile_add(v, ys)
 
 
 # --------------------------------------------------------------------------- class-conditional fgan128

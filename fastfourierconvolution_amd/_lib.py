@@ -232,6 +232,11 @@ SIGNATURES = [
                                        c_void_p]),
     ("ffc_embed_gather_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("ffc_embed_scatter_rows", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_lfu_gather", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                               c_void_p]),
+    ("ffc_lfu_tile_add", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_lfu_gather_bwd", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_lfu_tile_bwd", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
 ]
 
 _lock = threading.Lock()

@@ -3,7 +3,7 @@ from .ffc_bn_act import FFC_BN_ACT
 from .ffc_transpose import FFCTranspose
 from .fourier_unity import FourierUnitSN
 from .snffc import SNFFC, SNFFCTranspose, set_mix_precision, spectral_norm_ffc
-from .spectral_transform import SELayer, SpectralTransform
+from .spectral_transform import SELayer, SpectralTransform, set_lfu
 
 __all__ = ["FFC", "FFC_BN_ACT", "FFCTranspose", "FourierUnitSN", "SELayer", "SpectralTransform", "SNFFC",
-           "SNFFCTranspose", "spectral_norm_ffc", "set_mix_precision"]
+           "SNFFCTranspose", "spectral_norm_ffc", "set_mix_precision", "set_lfu"]

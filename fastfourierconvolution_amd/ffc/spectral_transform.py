@@ -2,7 +2,8 @@
 
 Same constructor signatures, submodule names (``downsample``, ``conv1``, ``bn1``, ``act1``, ``fu``,
 ``lfu``, ``conv2``, ``se_block``) and state_dict keys.  ``lfu`` is constructed (its parameters
-are in the reference's checkpoints) but never executed, exactly as in the reference (:94-105).
+are in the reference's checkpoints) and, as in the reference (:94-105), not executed unless
+``run_lfu`` is switched on (``set_lfu``; off by default).
 
 HIP execution of forward (x -> conv2(s + fu(s))):
   1. SE gate per sample (mean over HW, two tiny FCs)                      ffc_se_gate
@@ -14,6 +15,14 @@ HIP execution of forward (x -> conv2(s + fu(s))):
   5. conv2 as a 1x1 GEMM (inside FFC/FFCTranspose this is folded into the local conv GEMM)
 SE, conv1 and train-mode BN1 commute with nearest upsampling, so steps 1-3 run at the input
 resolution; the running-var unbiasing uses the upsampled count (count_mult = 4).
+
+With ``run_lfu`` the local Fourier unit -- the call the reference keeps in a comment (:94-108) -- runs
+too: forward is conv2(s + fu(s) + tile(lfu(xs))), xs (B, c, H/2, W/2) the four quadrants (top-left,
+bottom-left, top-right, bottom-right) of the first c/4 channels of s stacked on the channel axis,
+tile = repeat(1, 1, 2, 2).  bn1 is then finalized by its own launch (both Fourier units read it), and
+  4a. xs gathered from the pre-BN conv1 output, bn1 + ReLU + upsample on load    ffc_lfu_gather
+  4b. ys = lfu(xs): the Fourier-unit kernels of step 4 on the quadrant stack     ffc_fu_forward
+  4c. v += tile(ys), in place on the tensor conv2 reads                          ffc_lfu_tile_add
 """
 import torch
 import torch.nn as nn
@@ -69,6 +78,7 @@ class SpectralTransform(nn.Module):
                                                     groups=groups, enable_lfu=enable_lfu, upsample=upsample,
                                                     num_classes=num_classes)]
         self.enable_lfu = enable_lfu
+        self.run_lfu = False   # execute the local Fourier unit (set_lfu); needs enable_lfu
         self.downsample = nn.Identity()
         if stride == 2 and upsample:
             self.downsample = nn.Upsample(scale_factor=2, mode="nearest")
@@ -121,8 +131,36 @@ class SpectralTransform(nn.Module):
             return 2, 1
         return 1, 1
 
+    def lfu_check(self, c, H, W):
+        """run_lfu on an (c, H, W) main plane: the (c, H/2, W/2) quadrant stack must be a plane the
+        Fourier unit runs -- checked before anything is launched"""
+        if not self.enable_lfu:
+            raise ValueError("SpectralTransform.run_lfu needs a module built with enable_lfu=True")
+        if self.lfu.mix_precision != "fp32":
+            raise NotImplementedError("the local Fourier unit computes its spectral mix in fp32 only "
+                                      f"(mix_precision={self.lfu.mix_precision!r} with run_lfu)")
+        L = rt.lib()
+        ok = c % 4 == 0 and H % 2 == 0 and W % 2 == 0 and H >= 2 and W >= 2
+        if ok:
+            ok = L.ffc_fu_supported(c, H // 2, W // 2, 1) == 1 or bool(L.ffc_fu2d_supported(c, H // 2, W // 2, 1))
+        if not ok:
+            raise NotImplementedError(
+                f"local Fourier unit: needs channels % 4 == 0, even H and W, and a ({c}, H/2, W/2) plane the "
+                f"Fourier unit runs (H/2 = W/2 in {{4, 8, 16, 32, 64, 128}} or 24x24 within its channel limits); "
+                f"got c={c}, {H}x{W} (LFU plane {H // 2}x{W // 2})")
+
+    def _run_lfu(self, t, up, sc1, sh1):
+        """ys = lfu(xs), xs the quadrant stack of s = relu(t * sc1 + sh1) (upsampled by ``up``)"""
+        B, c, h, w = t.shape
+        xs = torch.empty((B, c, h * up // 2, w * up // 2), device=t.device, dtype=torch.float32)
+        with rt.observe("lfu_gather", bytes=4.0 * (t.numel() // 4 + xs.numel())):
+            check(rt.lib().ffc_lfu_gather(ptr(t), B, c, h, w, up, ptr(sc1), ptr(sh1), 1, ptr(xs), rt.stream_of(t)),
+                  "ffc_lfu_gather")
+        return self.lfu._run(xs)
+
     def spectral(self, x):
-        """v = s + fu(s), s = relu(bn1(conv1(se(downsample(x))))) — the part of forward before conv2."""
+        """v = s + fu(s) [+ tile(lfu(xs)) with run_lfu], s = relu(bn1(conv1(se(downsample(x))))) — the part
+        of forward before conv2."""
         x = rt.require(x, "x")
         if self.groups != 1:
             raise NotImplementedError("grouped SpectralTransform (groups != 1) is not on the hot path")
@@ -136,6 +174,8 @@ class SpectralTransform(nn.Module):
             raise NotImplementedError("AvgPool2d(2) downsample of an odd-sized input")
         h2, w2 = (H // 2, W // 2) if pool else (H, W)
         c = self.conv1.out_channels
+        if self.run_lfu:
+            self.lfu_check(c, h2 * up, w2 * up)
         dev = x.device
         stream = rt.stream_of(x)
         use_batch, _ = rt.bn_mode(self.bn1)
@@ -179,13 +219,19 @@ class SpectralTransform(nn.Module):
             nrows = lp.stat_rows(0)
             slab = torch.empty((nrows, c, 4), device=dev, dtype=torch.float32) if use_batch else None
             lp.launch([ex.job([(x, gate)], t, stats=slab)], stream, flops=ex.flops)
-        fold = rt.bn_fold(self.bn1, c, slab, nrows, float(up * up), dev) if use_batch else None
-        if fold is None and use_batch:   # the staged FU's r2c can still fold it channel by channel
+        # run_lfu: bn1 has two consumers (fu and the LFU gather), so it is finalized by its own launch
+        can_fold = use_batch and not self.run_lfu
+        fold = rt.bn_fold(self.bn1, c, slab, nrows, float(up * up), dev) if can_fold else None
+        if fold is None and can_fold:   # the staged FU's r2c can still fold it channel by channel
             fold = rt.bn_fold_channels(self.bn1, c, slab, nrows, float(up * up), dev)
         if fold is not None:   # bn1 finalized inside the FU's first kernel
             return self.fu._run(t, up=up, in_relu=True, residual=True, in_fold=fold)
         sc1, sh1 = rt.bn_scale_shift(self.bn1, c, slab, nrows if use_batch else 0, float(up * up), dev, stream)
-        return self.fu._run(t, up=up, in_scale=sc1, in_shift=sh1, in_relu=True, residual=True)
+        if not self.run_lfu:
+            return self.fu._run(t, up=up, in_scale=sc1, in_shift=sh1, in_relu=True, residual=True)
+        ys = self._run_lfu(t, up, sc1, sh1)
+        v = self.fu._run(t, up=up, in_scale=sc1, in_shift=sh1, in_relu=True, residual=True)
+        return ag.lfu_tile_add_impl(v, ys, out=v)
 
     def forward(self, x, y=None):
         if y is not None:
@@ -214,3 +260,19 @@ class SpectralTransform(nn.Module):
         out = torch.empty((B, self.conv2.out_channels, H, W), device=v.device, dtype=torch.float32)
         lp.launch([ex.job([(v, None)], out)], rt.stream_of(v), flops=ex.flops)
         return out
+
+
+def set_lfu(model: nn.Module, on: bool = True) -> nn.Module:
+    """Switch the local Fourier unit of every SpectralTransform in ``model`` on (or off): forward becomes
+    conv2(s + fu(s) + tile(lfu(quadrants of s))) instead of conv2(s + fu(s)).  Off by default, as in the
+    reference, which never executes this branch.  The ``lfu`` parameters exist either way, so
+    checkpoints load the same.  Raises ValueError for a SpectralTransform built with enable_lfu=False;
+    a plane the LFU cannot run raises NotImplementedError at the first forward.  Returns ``model``."""
+    sts = [m for m in model.modules() if isinstance(m, SpectralTransform)]
+    for m in sts:
+        if on and not m.enable_lfu:
+            raise ValueError("set_lfu: a SpectralTransform of this model was built with enable_lfu=False "
+                             "(it has no lfu parameters to run)")
+    for m in sts:
+        m.run_lfu = bool(on)
+    return model

@@ -15,6 +15,9 @@ Training ops (autograd): one per op the reference's forward is made of (see _aut
   ffc::rfft2           rfftn(ortho) + Re/Im interleave (fourier_unity.py:38-42)   backward: ffc::irfft2
   ffc::irfft2          de-interleave + irfftn(s=(H, W), ortho) (:51-56) [+ x]     backward: ffc::rfft2
   ffc::noise_inject    NoiseInjection (layers/noise_injection.py:25-32)  backward: ffc::noise_wgrad
+  ffc::lfu_split       quadrant stack of the local Fourier unit (spectral_transform.py:96-101, a comment
+                       there; run with set_lfu)                     backward: ffc::lfu_split_backward
+  ffc::lfu_tile_add    v + its output repeated 2 x 2 (:104-108)     backward: ffc::lfu_tile_backward
 
 Inference ops (the fused kernels; used under torch.no_grad() / when nothing needs a gradient):
   ffc::ffc_bn_act      one FFC_BN_ACT / FFC / FFCTranspose layer (ffc_bn_act.py:70-83, ffc.py:84-99,
@@ -298,6 +301,58 @@ def _irfft2_bwd(ctx, dy):
 rfft2.register_autograd(_rfft2_bwd, setup_context=_rfft2_setup)
 irfft2.register_autograd(_irfft2_bwd, setup_context=_irfft2_setup)
 
+# ---------------------------------------------------------------- ffc::lfu_split / ffc::lfu_tile_add
+# the data movement of SpectralTransform's local Fourier unit (csrc/lfu_kernels.hip)
+
+
+@torch.library.custom_op("ffc::lfu_split", mutates_args=())
+def lfu_split(s: Tensor) -> Tensor:
+    """(B, c, H, W) -> the quadrants of the first c/4 channels stacked on the channel axis (B, c, H/2, W/2)"""
+    return ag.lfu_split_impl(s)
+
+
+@lfu_split.register_fake
+def _(s):
+    return s.new_empty((s.shape[0], s.shape[1], s.shape[2] // 2, s.shape[3] // 2))
+
+
+@torch.library.custom_op("ffc::lfu_split_backward", mutates_args=())
+def lfu_split_backward(dxs: Tensor) -> Tensor:
+    return ag.lfu_split_backward_impl(dxs)
+
+
+@lfu_split_backward.register_fake
+def _(dxs):
+    return dxs.new_empty((dxs.shape[0], dxs.shape[1], 2 * dxs.shape[2], 2 * dxs.shape[3]))
+
+
+@torch.library.custom_op("ffc::lfu_tile_add", mutates_args=())
+def lfu_tile_add(v: Tensor, ys: Tensor) -> Tensor:
+    """v (B, c, H, W) + ys (B, c, H/2, W/2) repeated 2 x 2 over the plane"""
+    return ag.lfu_tile_add_impl(v, ys)
+
+
+@lfu_tile_add.register_fake
+def _(v, ys):
+    return torch.empty_like(v)
+
+
+@torch.library.custom_op("ffc::lfu_tile_backward", mutates_args=())
+def lfu_tile_backward(dv: Tensor) -> Tensor:
+    return ag.lfu_tile_backward_impl(dv)
+
+
+@lfu_tile_backward.register_fake
+def _(dv):
+    return dv.new_empty((dv.shape[0], dv.shape[1], dv.shape[2] // 2, dv.shape[3] // 2))
+
+
+# split <-> split_backward are each other's adjoints (a permutation and its zero-filled inverse);
+# tile_add passes the gradient through to v and sums its four quadrants for ys
+lfu_split.register_autograd(lambda ctx, dxs: torch.ops.ffc.lfu_split_backward(dxs))
+lfu_split_backward.register_autograd(lambda ctx, ds: torch.ops.ffc.lfu_split(ds))
+lfu_tile_add.register_autograd(lambda ctx, dv: (dv, torch.ops.ffc.lfu_tile_backward(dv)))
+
 # ---------------------------------------------------------------- ffc::noise_inject
 
 
@@ -505,6 +560,8 @@ def _module_state(m: nn.Module):
             e += [sub.approximate]
         elif hasattr(sub, "mix_precision"):
             e += [sub.mix_precision]
+        elif getattr(sub, "run_lfu", False):   # a SpectralTransform running its local Fourier unit: another
+            e += ["run_lfu"]                   # spec, so another template and plan (off: the spec is unchanged)
         out.append(e)
     return out
 
@@ -557,6 +614,8 @@ class _Template:
                 sub.approximate = e[2]
             elif len(e) > 2 and hasattr(sub, "mix_precision"):
                 sub.mix_precision = e[2]
+            elif len(e) > 2 and e[2] == "run_lfu" and hasattr(sub, "run_lfu"):
+                sub.run_lfu = True
         self.kind, self.module = kind, mod
         self.param_names = [n for n, _ in mod.named_parameters()]
         self.buffer_names = [n for n, _ in mod.named_buffers()]

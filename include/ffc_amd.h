@@ -662,6 +662,32 @@ int ffc_embed_gather_rows(const float* table, const int64_t* labels, int B, int 
 int ffc_embed_scatter_rows(const float* grad, const int64_t* labels, int B, int num_classes, int D, float* dtable,
                            void* stream);
 
+/* ------------------------------------------------------------------ local Fourier unit (LFU)
+ * The semi-global branch of SpectralTransform (layers/ffc/spectral_transform.py:94-108, sketched in a
+ * comment there and never executed by the reference).  With s = relu(bn1(conv1(.))) (B, c, H, W):
+ *   xs (B, c, H/2, W/2): channel k = quadrant k / (c/4) of channel k % (c/4) of s; quadrants in the
+ *                        order top-left, bottom-left, top-right, bottom-right
+ *   ys = lfu(xs)         a FourierUnitSN: the ffc_fu_* / ffc_fu2d_* entry points on xs
+ *   v  = s + fu(s) + ys tiled 2 x 2 over the plane                      (what conv2 reads)
+ * The four entry points below are the data movement around the Fourier unit.  c % 4 == 0, H and W
+ * even; 16-byte accesses when W/2 % 4 == 0 and the tensors are 16-byte aligned, 4-byte otherwise; no
+ * atomics.  Pure additions: ffc_abi_version() stays 4 (no existing signature or struct changed, so
+ * no caller breaks). */
+/* xs from the pre-BN t (B, c, h, w), H = h * up, W = w * up, up in {1, 2} (the transposed layers'
+ * nearest upsample): the Fourier unit's input transform -- t * in_scale[ch] + in_shift[ch] (either
+ * may be NULL: 1 / 0), then ReLU when in_relu -- applied on load */
+int ffc_lfu_gather(const float* t, int B, int c, int h, int w, int up, const float* in_scale, const float* in_shift,
+                   int in_relu, float* xs, void* stream);
+/* out[b][k][i][j] = v[b][k][i][j] + ys[b][k][i % (H/2)][j % (W/2)], v and out (B, c, H, W); out may
+ * be v (in place).  One fp32 add per element: exact. */
+int ffc_lfu_tile_add(const float* v, const float* ys, int B, int c, int H, int W, float* out, void* stream);
+/* adjoint of ffc_lfu_gather (up = 1, identity transform) from dxs (B, c, H/2, W/2): ds (B, c, H, W)
+ * is OVERWRITTEN -- the quadrants back in channels [0, c/4), zeros in [c/4, c).  A permutation. */
+int ffc_lfu_gather_bwd(const float* dxs, int B, int c, int H, int W, float* ds, void* stream);
+/* adjoint of the tiling from dv (B, c, H, W): dys[b][k][i][j] = (dv[i][j] + dv[i][j + W/2]) +
+ * (dv[i + H/2][j] + dv[i + H/2][j + W/2]): a fixed order, bitwise reproducible */
+int ffc_lfu_tile_bwd(const float* dv, int B, int c, int H, int W, float* dys, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
