@@ -7,19 +7,23 @@ exports FourierUnitSN, SELayer, SpectralTransform, FFC, FFCTranspose, FFC_BN_ACT
 Print, debug_print, NoiseInjection, GaussianNoise (the names layers/__init__.py:2-18 exports for this path)
 plus the restated callers FFCModel / FFCGenerator / FFCDiscriminator / FGenerator and Discriminator (fgan128), the
 class-conditional FCondGenerator / FCondDiscriminator (fgan128_cond_complete.py) and the 8*mg family
-FGenerator32 / Discriminator32 / FDiscriminator32 (fgan_complete.py; 32x32 at mg = 4, 48x48 at mg = 6).  All compute runs in
+FGenerator32 / Discriminator32 / FDiscriminator32 (fgan_complete.py; 32x32 at mg = 4, 48x48 at mg = 6) with its
+conditional-batch-norm variant ConditionalBatchNorm2d / FCondGenerator32 / FCondGeneratorSTL / CondDiscriminator32 /
+FCondDiscriminator32 (layers/cond/cond_bn.py, fgan_cond_complete.py; set_cond_bn).  All compute runs in
 the gfx950 HIP library libffc_amd.so (include/ffc_amd.h); there is no CPU fallback.
 """
 from . import ops  # noqa: F401  (registers the torch.ops.ffc.* custom ops)
 from .config import Config
-from .ffc import (FFC, FFC_BN_ACT, SNFFC, FFCTranspose, FourierUnitSN, SELayer, SNFFCTranspose, SpectralTransform,
-                  set_lfu, set_mix_precision, spectral_norm_ffc)
+from .ffc import (FFC, FFC_BN_ACT, SNFFC, ConditionalBatchNorm2d, FFCTranspose, FourierUnitSN, SELayer,
+                  SNFFCTranspose, SpectralTransform, set_cond_bn, set_lfu, set_mix_precision, spectral_norm_ffc)
 from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
-from .models import (Discriminator, Discriminator32, FCondDiscriminator, FCondGenerator, FDiscriminator32,
-                     FFCDiscriminator, FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32)
+from .models import (CondDiscriminator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
+                     FCondGenerator, FCondGenerator32, FCondGeneratorSTL, FDiscriminator32, FFCDiscriminator,
+                     FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32)
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
            "SNFFCTranspose", "spectral_norm_ffc", "set_mix_precision", "set_lfu", "Resizer",
            "Print", "debug_print", "NoiseInjection", "FFCModel", "FFCGenerator", "FFCDiscriminator", "FGenerator",
            "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "FGenerator32",
-           "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config"]
+           "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",
+           "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32"]

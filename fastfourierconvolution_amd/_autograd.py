@@ -846,6 +846,131 @@ def embed_rows_backward_impl(grad, labels, num_classes):
     return out
 
 
+# --------------------------------------------------------------------------- conditional batch norm
+def cbn_act_impl(x, labels, embed, running_mean, running_var, use_batch, eps, act, param, noise_w, noise):
+    """ffc::cbn_act: y = act(BN0(x) * gamma[labels] + beta[labels]) [+ noise_w * noise], BN0 the
+    affine-less nn.BatchNorm2d normalisation (batch statistics when use_batch, else the running ones)
+    and (gamma | beta) the halves of embed's rows (layers/cond/cond_bn.py:16-24).
+    -> [y, scale0, shift0, stats]: stats as ffc::bn_act returns them"""
+    x = rt.require(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"cbn_act: x must be (B, C, H, W), got {tuple(x.shape)}")
+    B, C = x.shape[:2]
+    HW = x.shape[2] * x.shape[3]
+    labels = _labels(labels, B, "cbn_act")
+    embed = rt.require(embed.detach(), "embed.weight")
+    if embed.dim() != 2 or embed.shape[1] != 2 * C:
+        raise RuntimeError(f"cbn_act: embed.weight must be (num_classes, {2 * C}), got {tuple(embed.shape)}")
+    if running_mean is not None and running_mean.numel() != C:
+        raise RuntimeError(f"running_mean should contain {C} elements not {running_mean.numel()}")
+    if use_batch and rt._sync_group() is not None:
+        raise NotImplementedError("ConditionalBatchNorm2d has no SyncBN path (its backward sums would need their "
+                                  "own all-reduce)")
+    if (noise_w is None) != (noise is None):
+        raise RuntimeError("cbn_act: noise_w and noise go together")
+    if noise is not None:
+        noise = rt.require(noise, "noise")
+        noise_w = rt.require(noise_w.detach(), "noise weight").reshape(-1)
+        if tuple(noise.shape) != (B, 1) + tuple(x.shape[2:]) or noise_w.numel() != C:
+            raise RuntimeError(f"cbn_act: noise must be {(B, 1) + tuple(x.shape[2:])} with {C} weights, got "
+                               f"{tuple(noise.shape)} / {noise_w.numel()}")
+    L = rt.lib()
+    dev, stream = x.device, _stream(x)
+    scale = torch.empty(C, device=dev, dtype=torch.float32)
+    shift = torch.empty(C, device=dev, dtype=torch.float32)
+    if use_batch:
+        S = L.ffc_reduce_splits(B, C, HW)
+        ws = torch.empty(S * C * 2, device=dev, dtype=torch.float64)
+        stats = torch.empty((C, 3), device=dev, dtype=torch.float64)
+        with rt.observe("bn_moments", bytes=4.0 * x.numel()):
+            check(L.ffc_channel_moments(ptr(x), B, C, HW, ptr(ws), S, ptr(stats), stream), "ffc_channel_moments")
+        check(L.ffc_bn_finalize(ptr(stats), C, None, None, None, None, None, 1, 0, 0.1, float(eps), 1.0, ptr(scale),
+                                ptr(shift), stream), "ffc_bn_finalize")
+    else:
+        stats = torch.stack((running_mean.detach(), running_var.detach())).float().contiguous()
+        check(L.ffc_bn_finalize(None, C, None, None, ptr(stats[0]), ptr(stats[1]), None, 0, 0, 0.1, float(eps), 1.0,
+                                ptr(scale), ptr(shift), stream), "ffc_bn_finalize")
+    y = torch.empty_like(x)
+    from ._lib import CbnApplyItem
+    item = (CbnApplyItem * 1)()
+    item[0] = CbnApplyItem(ptr(x), ptr(y), B, C, HW, embed.shape[0], ptr(scale), ptr(shift), ptr(embed), ptr(labels),
+                           int(act), float(param), ptr(noise_w), ptr(noise))
+    with rt.observe("cbn_act", bytes=8.0 * x.numel() + (4.0 * noise.numel() if noise is not None else 0.0)):
+        check(L.ffc_cbn_act_apply_batch(item, 1, stream), "ffc_cbn_act_apply_batch")
+    return [y, scale, shift, stats]
+
+
+def cbn_act_backward_impl(x, dy, labels, embed, scale, shift, use_batch, act, param, need_dx, need_embed):
+    """ffc::cbn_act_backward -> [dx, d embed] (empty tensors where not needed).  Two passes over x and
+    dy (per-sample sums, then dx); d embed is the row scatter of the sums: sample order, no atomics,
+    exact zeros for classes absent from the batch"""
+    x = x.contiguous()
+    dy = dy.contiguous()
+    B, C = x.shape[:2]
+    HW = x.shape[2] * x.shape[3]
+    labels = labels.contiguous()
+    embed = embed.detach().contiguous()
+    K = embed.shape[0]
+    L = rt.lib()
+    dev, stream = x.device, _stream(x)
+    args = (ptr(x), ptr(dy), ptr(labels), ptr(embed), B, C, HW, K, ptr(scale), ptr(shift), int(act), float(param))
+    dx = dembed = coef = None
+    if need_embed or (need_dx and use_batch):
+        sums = torch.empty((B, 2 * C), device=dev, dtype=torch.float32)
+        with rt.observe("cbn_bwd", bytes=8.0 * x.numel()):
+            check(L.ffc_cbn_bwd_sums(*args, ptr(sums), stream), "ffc_cbn_bwd_sums")
+        if need_embed:
+            dembed = torch.empty((K, 2 * C), device=dev, dtype=torch.float32)
+            check(L.ffc_embed_scatter_rows(ptr(sums), ptr(labels), B, K, 2 * C, ptr(dembed), stream),
+                  "ffc_embed_scatter_rows")
+        if need_dx and use_batch:
+            coef = torch.empty((C, 2), device=dev, dtype=torch.float32)
+            check(L.ffc_cbn_bwd_coeff(ptr(sums), ptr(labels), ptr(embed), B, C, HW, K, ptr(coef), stream),
+                  "ffc_cbn_bwd_coeff")
+    if need_dx:
+        dx = torch.empty_like(x)
+        with rt.observe("cbn_bwd", bytes=12.0 * x.numel()):
+            check(L.ffc_cbn_bwd_apply(*args, ptr(coef), ptr(dx), stream), "ffc_cbn_bwd_apply")
+    return [t if t is not None else x.new_empty(0) for t in (dx, dembed)]
+
+
+def cbn_labels(y, what="ConditionalBatchNorm2d"):
+    """the reference's double torch.squeeze of the label argument (cond_bn.py:17-18) -> (B,) int64
+    device labels; a 0-d result (B == 1) fails as the reference's chunk(2, 1) does"""
+    if not isinstance(y, torch.Tensor):
+        raise TypeError(f"{what}: labels must be a tensor, got {type(y).__name__}")
+    if not y.is_cuda:
+        raise FFCError(f"{what}: labels must be on a ROCm/HIP device (there is no CPU fallback)")
+    y = torch.squeeze(torch.squeeze(y))
+    if y.dim() == 0:
+        raise IndexError("Dimension out of range (expected to be in range of [-1, 0], but got 1)")
+    return y
+
+
+def cbn_act(cbn, x, y, act=(0, 0.0), noise=None):
+    """ConditionalBatchNorm2d ``cbn`` + activation (+ the NoiseInjection (module, noise) that follows) on
+    the ffc::cbn_act op, then nn.BatchNorm2d's running-statistics update in training mode"""
+    bn = cbn.bn
+    if bn.weight is not None:
+        raise NotImplementedError("ConditionalBatchNorm2d wraps an affine-less BatchNorm2d")
+    labels = cbn_labels(y)
+    use_batch, update = rt.bn_mode(bn)
+    nw = nz = None
+    if noise is not None:
+        mod, nz = noise
+        if nz is None:
+            nz = x.new_empty(x.shape[0], 1, x.shape[2], x.shape[3]).normal_()
+        nw = mod.weight
+    out, _, _, stats = torch.ops.ffc.cbn_act(x, labels, cbn.embed.weight, bn.running_mean, bn.running_var, use_batch,
+                                             float(bn.eps), int(act[0]), float(act[1]), nw, nz)
+    if update:
+        torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked, stats,
+                                        -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
+    if RECORD is not None:
+        RECORD.append(out.detach())
+    return out
+
+
 def cond_stem(mod, z, labels):
     """FCondGenerator's stem over its modules (input_conv, label_conv, label_embed) on ffc::cond_stem,
     then nn.BatchNorm2d's running-statistics updates in training mode"""

@@ -94,6 +94,13 @@ class BnApplyItem(ctypes.Structure):
                 ("plane_sum", c_void_p)]
 
 
+class CbnApplyItem(ctypes.Structure):
+    """ffc_cbn_apply_item: one tensor of ffc_cbn_act_apply_batch"""
+    _fields_ = [("x", c_void_p), ("y", c_void_p), ("B", c_int), ("C", c_int), ("HW", c_int), ("num_classes", c_int),
+                ("scale0", c_void_p), ("shift0", c_void_p), ("embed", c_void_p), ("labels", c_void_p), ("act", c_int),
+                ("act_param", c_float), ("noise_w", c_void_p), ("noise", c_void_p)]
+
+
 # (name, restype, argtypes) for every entry point declared in include/ffc_amd.h
 SIGNATURES = [
     ("ffc_last_error", ctypes.c_char_p, []),
@@ -237,6 +244,12 @@ SIGNATURES = [
     ("ffc_lfu_tile_add", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("ffc_lfu_gather_bwd", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("ffc_lfu_tile_bwd", c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_cbn_act_apply_batch", c_int, [ctypes.POINTER(CbnApplyItem), c_int, c_void_p]),
+    ("ffc_cbn_bwd_sums", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                 c_void_p, c_int, c_float, c_void_p, c_void_p]),
+    ("ffc_cbn_bwd_coeff", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_cbn_bwd_apply", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
 ]
 
 _lock = threading.Lock()
@@ -263,11 +276,11 @@ def load(path: str | None = None):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        sizes = (c_int * 10)()
-        lib.ffc_struct_sizes(sizes, 10)
+        sizes = (c_int * 11)()
+        lib.ffc_struct_sizes(sizes, 11)
         want = (ctypes.sizeof(ConvSeg), ctypes.sizeof(ConvPhase), ctypes.sizeof(ConvJob),
                 ctypes.sizeof(ConvPSeg), ctypes.sizeof(ConvPPhase), ctypes.sizeof(ConvPJob), ctypes.sizeof(BnFold),
-                ctypes.sizeof(InTf), ctypes.sizeof(BnRfItem), ctypes.sizeof(BnApplyItem))
+                ctypes.sizeof(InTf), ctypes.sizeof(BnRfItem), ctypes.sizeof(BnApplyItem), ctypes.sizeof(CbnApplyItem))
         if tuple(sizes) != want:
             raise FFCError(f"ABI struct layout mismatch: library {tuple(sizes)} vs binding {want}")
         _lib = lib

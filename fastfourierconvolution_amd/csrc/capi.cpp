@@ -69,5 +69,6 @@ extern "C" int ffc_struct_sizes(int* out, int n) {
         out[8] = (int)sizeof(ffc_bn_rf_item);
         out[9] = (int)sizeof(ffc_bn_apply_item);
     }
+    if (n >= 11) out[10] = (int)sizeof(ffc_cbn_apply_item);
     return FFC_OK;
 }

@@ -9,7 +9,9 @@ rejects, models/ffcmodel.py:17) is accepted and ignored.
 
 The 8*mg family of fgan_complete.py (32x32 at mg = 4; 48x48 STL-10 / flowers / CelebA at mg = 6) is
 restated as FGenerator32, Discriminator32 and FDiscriminator32: ``FGenerator`` and ``Discriminator``
-name the fgan128 classes here.
+name the fgan128 classes here.  Its class-conditional variant, fgan_cond_complete.py (conditional batch
+norm on bn_l / bn_g of every FFC_BN_ACT), is FCondGenerator32, FCondGeneratorSTL, CondDiscriminator32
+and FCondDiscriminator32.
 """
 import os
 
@@ -21,7 +23,7 @@ from . import _runtime as rt
 from ._lib import check, ptr
 from . import _plan
 from .config import Config
-from .ffc import FFC_BN_ACT
+from .ffc import FFC_BN_ACT, ConditionalBatchNorm2d, set_cond_bn
 from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
 
 # FGenerator conv6 -> conv7 hand-off with the BN + GELU + noise pass deferred into the head's operand
@@ -151,12 +153,13 @@ class FGenerator(FFCModel):
         self.noise_to_feature = nn.Sequential(nn.Linear(z_size, (self.mg * self.mg) * self.ngf * 8))
         self._build_trunk(ngf, ratio_g)
 
-    def _build_trunk(self, ngf, ratio_g):
+    def _build_trunk(self, ngf, ratio_g, **norm):
         """conv2..conv6 (x2 FFC_BN_ACT + NoiseInjection pairs) and the conv7 head at width ngf and global
         ratio ratio_g (fgan128_complete.py:457-488; fgan128_cond_complete.py:43-70 at ngf = 64, 0.25);
         conv2..conv4 and the conv5 head for the 8*mg family (UPS / HEAD; fgan_complete.py:97-113)"""
         T = dict(activation_layer=nn.GELU, norm_layer=nn.BatchNorm2d, upsampling=True, uses_noise=True,
                  uses_sn=self.USES_SN)
+        T.update(norm)   # the conditional 8*mg generators: norm_layer=ConditionalBatchNorm2d, num_classes=K
         plan = ((2, ngf * 8, ngf * 4, 0.0), (3, ngf * 4, ngf * 2, ratio_g), (4, ngf * 2, ngf, ratio_g),
                 (5, ngf, ngf, ratio_g), (6, ngf, ngf, ratio_g))[:len(self.UPS)]
         for n, cin, cout, rin in plan:
@@ -395,19 +398,163 @@ class FCondDiscriminator(Discriminator):
         side = 32 * self.mg
         if x.dim() != 4 or tuple(x.shape[1:]) != (3, side, side) or side != 128:
             raise RuntimeError(f"FCondDiscriminator: x must be (B, 3, 128, 128) with mg = 4, got {tuple(x.shape)}")
+        return _label_plane_critic(self, x, labels, side)
+
+
+def _label_plane_critic(self, x, labels, side):
+    """the label-conditioned plain critic on a (B, 3, side, side) image: label_embed's row of each sample's
+    class as a fourth input plane of conv1, then conv2.. and fc (fgan128_cond_complete.py:159-178,
+    fgan_cond_complete.py:211-227)"""
+    B = x.shape[0]
+    act, param = rt.act_code(self.act)
+    plane = torch.ops.ffc.embed_rows(self.label_embed.weight, labels).view(B, 1, side, side)
+    conv = self.conv1
+    rt.sn_refresh_train(conv)   # the slices below must see this call's W / sigma
+    k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+    (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)],
+                         [(0, 0, _plan.Seg("conv", 3, side, side, k, s, p), _ConvSlice(conv.weight, 0, 3, conv.bias)),
+                          (0, 1, _plan.Seg("conv", 1, side, side, k, s, p), _ConvSlice(conv.weight, 3, 4, None))],
+                         [x, plane])
+    for i in range(2, len(self.CONVS) + 1):
+        conv = getattr(self, f"conv{i}")
+        B, C, H, W = m.shape
+        sg = _plan.Seg("conv", C, H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+        (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)], [(0, 0, sg, conv)], [m])
+    return ag.linear(self.fc, m.reshape(m.shape[0], -1))
+
+
+# --------------------------------------------------------------------------- conditional 8*mg family
+class FCondGenerator32(FCondGenerator):
+    """fgan_cond_complete.py:33-114 (``FCondGenerator`` there): FCondGenerator's (B, 512, 4, 4) label / noise
+    stem (ffc::cond_stem), then conv2..conv4 -- x2 FFC_BN_ACT with ConditionalBatchNorm2d on bn_l / bn_g,
+    GELU and train-mode NoiseInjection -- and the 3x3 Tanh head conv5: a 32x32 image whatever ``mg`` (the
+    stem is 4x4; ``mg`` is stored as the reference stores it).  Built with ``cond_bn_only`` on
+    (set_cond_bn): the labels condition bn_l / bn_g only, which is what the reference's constructors
+    build; its forward as written raises TypeError in conv3.  Attribute names and state_dict keys are the
+    reference's.  ``forward(z, labels, noises=None)`` as FCondGenerator, noises [(lcl, glb)] * 3."""
+
+    UPS = (2, 3, 4)
+    HEAD = 5
+
+    def __init__(self, z_size, mg: int = 4, num_classes: int = 10):
+        FFCModel.__init__(self)
+        self.z_size = z_size
+        self.ngf = 64
+        self.mg = mg
+        self.num_classes = num_classes
+        self._build_trunk(self.ngf, 0.25, norm_layer=ConditionalBatchNorm2d, num_classes=num_classes)
+        self._build_stem(z_size, num_classes)
+        set_cond_bn(self)
+
+    def _build_stem(self, z_size, num_classes):
+        self.label_conv = nn.Sequential(nn.ConvTranspose2d(num_classes, self.ngf * 4, 4, 1, 0),
+                                        nn.BatchNorm2d(self.ngf * 4), nn.GELU())
+        self.input_conv = nn.Sequential(nn.ConvTranspose2d(z_size, self.ngf * 4, 4, 1, 0),
+                                        nn.BatchNorm2d(self.ngf * 4), nn.GELU())
+        self.label_embed = nn.Embedding(num_classes, num_classes)
+
+    def _trunk_cond(self, fake, labels, noises=None):
+        """conv2..conv4 with the labels + the conv5 head + Resizer (:104-114)"""
+        for i, n in enumerate(self.UPS):
+            conv = getattr(self, f"conv{n}")
+            if self.training:   # NoiseInjection fused into the conditional norm + GELU pass
+                nl, ng = noises[i] if noises is not None else (None, None)
+                fake = conv.forward_noise(fake, (getattr(self, f"lcl_noise{n}"), nl),
+                                          (getattr(self, f"glb_noise{n}"), ng), labels)
+            else:
+                fake = conv(fake, labels)
+        return self.resizer(getattr(self, f"conv{self.HEAD}")(fake))
+
+    def forward_float(self, z, labels, noises=None):
+        return self._trunk_cond(self._stem(z, labels), labels, noises)
+
+
+class FCondGeneratorSTL(FCondGenerator32):
+    """fgan_cond_complete.py:117-186: the conditional generator of the 8*mg planes (48x48 at mg = 6).
+    noise_to_feature = Linear(z_size + num_classes, mg*mg*512) on cat([z, label_embed[labels]]) -- the
+    row gather on ffc::embed_rows, the Linear as one two-segment GEMM job over its weight's two column
+    blocks (the concatenation is never built) -- viewed (512, mg, mg); then FCondGenerator32's trunk."""
+
+    def _build_stem(self, z_size, num_classes):
+        self.label_embed = nn.Embedding(num_classes, num_classes)
+        self.noise_to_feature = nn.Linear(z_size + num_classes, (self.mg * self.mg) * self.ngf * 8)
+
+    def _stem(self, z, labels):
+        z = rt.require(z, "z")
+        if z.dim() != 2 or z.shape[1] != self.z_size:
+            raise RuntimeError(f"FCondGeneratorSTL: z must be (B, {self.z_size}), got {tuple(z.shape)}")
+        B, K = z.shape[0], self.num_classes
+        emb = torch.ops.ffc.embed_rows(self.label_embed.weight, labels)                     # :160
+        lin = self.noise_to_feature
+        N = lin.out_features
+        w = lin.weight.view(N, self.z_size + K, 1, 1)
+        (f,) = ag.conv_layer(B, [(N, 0, 0.0)],
+                             [(0, 0, _plan.Seg("pw", self.z_size, 1, 1), _ConvSlice(w, 0, self.z_size, lin.bias)),
+                              (0, 1, _plan.Seg("pw", K, 1, 1), _ConvSlice(w, self.z_size, self.z_size + K, None))],
+                             [z.reshape(B, self.z_size, 1, 1), emb.reshape(B, K, 1, 1)])   # :164-165
+        return f.reshape(B, -1, self.mg, self.mg)                                           # :168
+
+
+class CondDiscriminator32(Discriminator32):
+    """fgan_cond_complete.py:189-227 (``Discriminator`` there): Discriminator32 whose conv1 reads a fourth
+    input plane, label_embed's (num_classes, 8mg*8mg) row of each sample's class (as FCondDiscriminator).
+    Input: (B, 3, 8*mg, 8*mg) fp32 and (B,) int64 labels on the GPU."""
+
+    CONVS = ((4, 64, 3, 1),) + Discriminator32.CONVS[1:]
+
+    def __init__(self, sn: bool = True, mg: int = 4, num_classes: int = 10):
+        super().__init__(sn=sn, mg=mg)
+        self.num_classes = num_classes
+        self.label_embed = nn.Embedding(num_classes, 8 * 8 * self.mg * self.mg)
+
+    def forward(self, x, labels):
+        x = rt.require(x, "x")
+        side = self.SIDE * self.mg
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, side, side):
+            raise RuntimeError(f"CondDiscriminator32: x must be (B, 3, {side}, {side}), got {tuple(x.shape)}")
+        return _label_plane_critic(self, x, labels, side)
+
+
+class FCondDiscriminator32(FFCModel):
+    """fgan_cond_complete.py:229-274 (``FDiscriminator`` there): the conditional FFC critic.  conv1..conv4
+    are FFC_BN_ACT with bias, global ratio 0.25 (conv4: local output only), LeakyReLU(0.1) and
+    ConditionalBatchNorm2d on bn_l / bn_g; the image passes GaussianNoise(0.05) (train mode) and is
+    joined by the label plane of label_embed (num_classes, 8mg*8mg) as a fourth channel; fc =
+    Linear(mg*mg*512, 1) under spectral norm when ``sn``.  Built with ``cond_bn_only`` on: conv2 and
+    conv3 have a SpectralTransform, where the reference's forward as written raises TypeError.
+    Input: (B, 3, 8*mg, 8*mg) fp32 and (B,) int64 labels on the GPU."""
+
+    def __init__(self, sn: bool = True, mg: int = 4, num_classes: int = 10):
+        super().__init__()
+        self.mg = mg
+        self.num_classes = num_classes
+        sn_fn = torch.nn.utils.spectral_norm if sn else (lambda m: m)
+        r = 0.25
+        L = dict(padding=1, bias=True, uses_noise=False, uses_sn=True, activation_layer=nn.LeakyReLU,
+                 norm_layer=ConditionalBatchNorm2d, num_classes=num_classes)
+        self.conv1 = FFC_BN_ACT(in_channels=3 + 1, out_channels=64, kernel_size=3, ratio_gin=0.0, ratio_gout=r,
+                                stride=1, **L)
+        self.conv2 = FFC_BN_ACT(in_channels=64, out_channels=128, kernel_size=4, ratio_gin=r, ratio_gout=r,
+                                stride=2, **L)
+        self.conv3 = FFC_BN_ACT(in_channels=128, out_channels=256, kernel_size=4, ratio_gin=r, ratio_gout=r,
+                                stride=2, **L)
+        self.conv4 = FFC_BN_ACT(in_channels=256, out_channels=512, kernel_size=4, ratio_gin=r, ratio_gout=0.0,
+                                stride=2, **L)
+        self.label_embed = nn.Embedding(num_classes, 8 * 8 * self.mg * self.mg)
+        self.fc = sn_fn(nn.Linear(self.mg * self.mg * 512, 1))
+        self.gaus_noise = GaussianNoise(0.05)
+        set_cond_bn(self)
+
+    def forward(self, x, labels):
+        x = rt.require(x, "x")
+        side = 8 * self.mg
+        if x.dim() != 4 or tuple(x.shape[1:]) != (3, side, side):
+            raise RuntimeError(f"FCondDiscriminator32: x must be (B, 3, {side}, {side}), got {tuple(x.shape)}")
         B = x.shape[0]
-        act, param = rt.act_code(self.act)
-        plane = torch.ops.ffc.embed_rows(self.label_embed.weight, labels).view(B, 1, side, side)   # :160-163
-        conv = self.conv1
-        rt.sn_refresh_train(conv)   # the slices below must see this call's W / sigma
-        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)],
-                             [(0, 0, _plan.Seg("conv", 3, side, side, k, s, p), _ConvSlice(conv.weight, 0, 3, conv.bias)),
-                              (0, 1, _plan.Seg("conv", 1, side, side, k, s, p), _ConvSlice(conv.weight, 3, 4, None))],
-                             [x, plane])                                                            # :167-169
-        for i in range(2, len(self.CONVS) + 1):
-            conv = getattr(self, f"conv{i}")
-            B, C, H, W = m.shape
-            sg = _plan.Seg("conv", C, H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
-            (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)], [(0, 0, sg, conv)], [m])
-        return ag.linear(self.fc, m.reshape(m.shape[0], -1))   # :178
+        x = self.gaus_noise(x)                                                              # :256
+        plane = torch.ops.ffc.embed_rows(self.label_embed.weight, labels).view(B, 1, side, side)   # :258-261
+        m = torch.cat([x, plane], dim=1)   # a 4-channel copy of the input image: data movement only
+        for conv in (self.conv1, self.conv2, self.conv3, self.conv4):                       # :265-268
+            m = conv(m, labels)
+        m = self.resizer(m)
+        return ag.linear(self.fc, m.reshape(-1, self.mg * self.mg * 512))                   # :271

@@ -496,6 +496,74 @@ def _embed_rows_bwd(ctx, g):
 
 embed_rows.register_autograd(_embed_rows_bwd, setup_context=_embed_rows_setup)
 
+# ---------------------------------------------------------------- ffc::cbn_act
+# ConditionalBatchNorm2d + activation (+ NoiseInjection) (layers/cond/cond_bn.py:16-24 inside
+# ffc_bn_act.py:70-83); labels as above: an int64 device tensor the kernels read
+
+
+@torch.library.custom_op("ffc::cbn_act", mutates_args=())
+def cbn_act(x: Tensor, labels: Tensor, embed: Tensor, running_mean: Optional[Tensor], running_var: Optional[Tensor],
+            use_batch: bool, eps: float, act: int, act_param: float, noise_w: Optional[Tensor],
+            noise: Optional[Tensor]) -> List[Tensor]:
+    """-> [y, scale0, shift0, stats]; functional (the running statistics are updated by
+    ffc::bn_update_running from stats).  noise_w / noise: the NoiseInjection that follows, or None (no
+    defaults in the schema: the dispatcher drops arguments equal to their default, and the backward
+    returns one gradient per argument)"""
+    return ag.cbn_act_impl(x, labels, embed, running_mean, running_var, use_batch, eps, act, act_param, noise_w,
+                           noise)
+
+
+@cbn_act.register_fake
+def _(x, labels, embed, running_mean, running_var, use_batch, eps, act, act_param, noise_w, noise):
+    C = x.shape[1]
+    stats = x.new_empty((C, 3), dtype=torch.float64) if use_batch else x.new_empty((2, C))
+    return [x.new_empty(x.shape), x.new_empty(C), x.new_empty(C), stats]
+
+
+@torch.library.custom_op("ffc::cbn_act_backward", mutates_args=())
+def cbn_act_backward(x: Tensor, dy: Tensor, labels: Tensor, embed: Tensor, scale: Tensor, shift: Tensor,
+                     use_batch: bool, act: int, act_param: float, need_dx: bool, need_embed: bool) -> List[Tensor]:
+    """-> [dx, d embed] (empty tensors where not needed)"""
+    return ag.cbn_act_backward_impl(x, dy, labels, embed, scale, shift, use_batch, act, act_param, need_dx,
+                                    need_embed)
+
+
+@cbn_act_backward.register_fake
+def _(x, dy, labels, embed, scale, shift, use_batch, act, act_param, need_dx, need_embed):
+    return [x.new_empty(x.shape) if need_dx else x.new_empty(0),
+            embed.new_empty(embed.shape) if need_embed else x.new_empty(0)]
+
+
+def _cbn_act_setup(ctx, inputs, output):
+    x, labels, embed, _, _, use_batch, _, act, act_param, noise_w, noise = inputs
+    _, scale, shift, stats = output
+    ctx.mark_non_differentiable(scale, shift, stats)
+    ctx.cfg = (bool(use_batch), int(act), float(act_param))
+    ctx.needs = (bool(x.requires_grad), bool(embed.requires_grad),
+                 noise_w is not None and bool(noise_w.requires_grad))
+    ctx.wshape = tuple(noise_w.shape) if noise_w is not None else None
+    ctx.has_noise = noise is not None
+    ctx.save_for_backward(x, labels, embed, scale, shift, *((noise,) if noise is not None else ()))
+
+
+def _cbn_act_bwd(ctx, grads):
+    dy = grads[0]
+    if dy is None:
+        return (None,) * 11
+    x, labels, embed, scale, shift = ctx.saved_tensors[:5]
+    use_batch, act, act_param = ctx.cfg
+    need_dx, need_embed, need_nw = ctx.needs
+    dx = dembed = dnw = None
+    if need_dx or need_embed:
+        dx, dembed = torch.ops.ffc.cbn_act_backward(x, dy, labels, embed, scale, shift, use_batch, act, act_param,
+                                                    need_dx, need_embed)
+    if need_nw:
+        dnw = torch.ops.ffc.noise_wgrad(dy, ctx.saved_tensors[5]).view(ctx.wshape)
+    return (dx if need_dx else None, None, dembed if need_embed else None) + (None,) * 6 + (dnw, None)
+
+
+cbn_act.register_autograd(_cbn_act_bwd, setup_context=_cbn_act_setup)
+
 # =========================================================================== inference ops
 
 

@@ -42,7 +42,8 @@ const char* ffc_last_error(void);
 int ffc_abi_version(void);
 /* sizeof(ffc_conv_seg), (ffc_conv_phase), (ffc_conv_job), (ffc_convp_seg), (ffc_convp_phase),
  * (ffc_convp_job) -> out[0..5]; n >= 7: sizeof(ffc_bn_fold) -> out[6]; n >= 8: sizeof(ffc_in_tf) -> out[7];
- * n >= 10: sizeof(ffc_bn_rf_item), sizeof(ffc_bn_apply_item) -> out[8], out[9] */
+ * n >= 10: sizeof(ffc_bn_rf_item), sizeof(ffc_bn_apply_item) -> out[8], out[9];
+ * n >= 11: sizeof(ffc_cbn_apply_item) -> out[10] */
 int ffc_struct_sizes(int* out, int n);
 
 /* ------------------------------------------------------------------ local branch
@@ -687,6 +688,52 @@ int ffc_lfu_gather_bwd(const float* dxs, int B, int c, int H, int W, float* ds, 
 /* adjoint of the tiling from dv (B, c, H, W): dys[b][k][i][j] = (dv[i][j] + dv[i][j + W/2]) +
  * (dv[i + H/2][j] + dv[i + H/2][j + W/2]): a fixed order, bitwise reproducible */
 int ffc_lfu_tile_bwd(const float* dv, int B, int c, int H, int W, float* dys, void* stream);
+
+/* ------------------------------------------------------------------ conditional batch norm
+ * ConditionalBatchNorm2d (layers/cond/cond_bn.py:6-24; bn_l / bn_g of an FFC_BN_ACT built with
+ * norm_layer=ConditionalBatchNorm2d, ffc_bn_act.py:70-83; the 8*mg conditional GANs of
+ * fgan_cond_complete.py): an affine-less BatchNorm2d whose scale and shift are, per sample, the two
+ * halves of row labels[b] of an nn.Embedding(num_classes, 2C) table.  labels: int64 DEVICE tensor (B),
+ * read by the kernels; a label outside [0, num_classes) touches no memory outside the table, makes
+ * that sample's forward outputs NaN and gets no row from ffc_embed_scatter_rows.  scale0 / shift0:
+ * the affine-less normalisation, ffc_bn_finalize / ffc_bn_reduce_finalize(_batch) with
+ * gamma = beta = NULL (scale0[c] = 1/sigma, shift0[c] = -mu/sigma).  Pure additions: the ABI version
+ * is unchanged. */
+/* y[b,c,:] = act((x*scale0[c] + shift0[c]) * E[l_b][c] + E[l_b][C+c]) + noise_w[c] * noise[b,:]
+ * for up to FFC_MAX_BN_BATCH tensors in one launch.  noise (B, 1, H, W) and noise_w (C) are both given
+ * or both NULL; in place (y == x) allowed; 16-byte accesses when HW % 4 == 0 and x / y / noise are
+ * 16-byte aligned, a 4-byte form otherwise (any HW >= 1). */
+typedef struct ffc_cbn_apply_item {
+    const float* x;
+    float* y;
+    int B, C, HW;
+    int num_classes;
+    const float* scale0;
+    const float* shift0;
+    const float* embed;        /* (num_classes, 2C): [gamma | beta] */
+    const int64_t* labels;     /* (B), device */
+    int act;
+    float act_param;
+    const float* noise_w;
+    const float* noise;
+} ffc_cbn_apply_item;
+int ffc_cbn_act_apply_batch(const ffc_cbn_apply_item* items, int n, void* stream);
+/* Backward.  g = dy * act'(z), xh = x*scale0 + shift0, z = xh*gamma_b + beta_b (act' taken at z: the
+ * values ffc_act_bwd gets from the output for ReLU / LeakyReLU / Tanh / Sigmoid and from the input
+ * for GELU).  ffc_cbn_bwd_sums: sums (B, 2C) fp32 = [sum_hw g*xh | sum_hw g] per sample, each sum in
+ * fp64 in a fixed order; the embedding gradient is ffc_embed_scatter_rows(sums, labels, B,
+ * num_classes, 2C, ...).  ffc_cbn_bwd_coeff: coef[C][2] = {m1, m2}, m1[c] = sum_b gamma_bc * s1[b][c]
+ * / (B*HW), m2 likewise from s2 (fp64, samples in order).  ffc_cbn_bwd_apply:
+ * dx = scale0[c] * (gamma_bc*g - m1[c] - xh*m2[c]); coef == NULL (eval mode, running statistics):
+ * dx = scale0[c] * gamma_bc * g. */
+int ffc_cbn_bwd_sums(const float* x, const float* dy, const int64_t* labels, const float* embed, int B, int C,
+                     int HW, int num_classes, const float* scale0, const float* shift0, int act, float act_param,
+                     float* sums, void* stream);
+int ffc_cbn_bwd_coeff(const float* sums, const int64_t* labels, const float* embed, int B, int C, int HW,
+                      int num_classes, float* coef, void* stream);
+int ffc_cbn_bwd_apply(const float* x, const float* dy, const int64_t* labels, const float* embed, int B, int C,
+                      int HW, int num_classes, const float* scale0, const float* shift0, int act, float act_param,
+                      const float* coef, float* dx, void* stream);
 
 #ifdef __cplusplus
 }
