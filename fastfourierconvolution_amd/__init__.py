@@ -15,14 +15,15 @@ the gfx950 HIP library libffc_amd.so (include/ffc_amd.h); there is no CPU fallba
 from . import ops  # noqa: F401  (registers the torch.ops.ffc.* custom ops)
 from .config import Config
 from .ffc import (FFC, FFC_BN_ACT, SNFFC, ConditionalBatchNorm2d, FFCTranspose, FourierUnitSN, SELayer,
-                  SNFFCTranspose, SpectralTransform, set_cond_bn, set_lfu, set_mix_precision, spectral_norm_ffc)
+                  SNFFCTranspose, SpectralTransform, set_cond_bn, set_lfu, set_mix_precision, set_sn_hip,
+                  spectral_norm_ffc)
 from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
 from .models import (CondDiscriminator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
                      FCondGenerator, FCondGenerator32, FCondGeneratorSTL, FDiscriminator32, FFCDiscriminator,
                      FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32)
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
-           "SNFFCTranspose", "spectral_norm_ffc", "set_mix_precision", "set_lfu", "Resizer",
+           "SNFFCTranspose", "spectral_norm_ffc", "set_sn_hip", "set_mix_precision", "set_lfu", "Resizer",
            "Print", "debug_print", "NoiseInjection", "FFCModel", "FFCGenerator", "FFCDiscriminator", "FGenerator",
            "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "FGenerator32",
            "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",

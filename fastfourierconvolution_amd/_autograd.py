@@ -995,3 +995,157 @@ def cond_stem(mod, z, labels):
                                             stats[k * STEM_CH:(k + 1) * STEM_CH],
                                             -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
     return y
+
+
+# --------------------------------------------------------------------------- spectral norm
+def sn_view(shape, dim):
+    """(M, K, R, stride_m, stride_i) of SpectralNorm.reshape_weight_to_matrix read in place
+    (ffc_sn_job): dim 0 is the dense (M, K) matrix, dim 1 of (d0, M, rest...) has
+    Wm[m, i * R + r] = W[i, m, r] with R = prod(rest)"""
+    shape = tuple(int(s) for s in shape)
+    n = 1
+    for s in shape:
+        n *= s
+    if len(shape) < 2 or n == 0:
+        raise NotImplementedError(f"spectral norm of a weight of shape {shape}")
+    if dim == 0 or (dim == 1 and shape[0] == 1):
+        M = shape[dim]
+        return M, n // M, n // M, n // M, 0
+    if dim != 1:
+        raise NotImplementedError(f"spectral norm over dim {dim} (dim 0: Conv2d / Linear, dim 1: ConvTranspose2d)")
+    M = shape[1]
+    R = n // (shape[0] * M)
+    return M, shape[0] * R, R, R, M * R
+
+
+def _sn_table(w_orig, dims, device):
+    """ffc_sn_job array with the views and workspace offsets filled in, and the workspace"""
+    from . import _lib
+    L = rt.lib()
+    jobs = (_lib.SnJob * len(w_orig))()
+    off = 0
+    for jb, w, dim in zip(jobs, w_orig, dims):
+        jb.M, jb.K, jb.R, jb.stride_m, jb.stride_i = sn_view(w.shape, dim)
+        need = L.ffc_sn_ws_bytes(jb.M, jb.K)
+        if not need:
+            raise NotImplementedError(f"spectral norm of a weight of shape {tuple(w.shape)}")
+        jb.ws_off = off
+        off += need
+    return jobs, torch.empty(off, device=device, dtype=torch.uint8)
+
+
+def _sn_check(ts, what, shapes=None):
+    for i, t in enumerate(ts):
+        rt.require(t, what)
+        if not t.is_contiguous():
+            raise FFCError(f"spectral norm: {what} must be contiguous")
+        if shapes is not None and t.numel() != shapes[i]:
+            raise RuntimeError(f"spectral norm: {what} has {t.numel()} elements, expected {shapes[i]}")
+
+
+def sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training):
+    """ffc::sn_weight: the spectral_norm pre-hook of len(w_orig) layers in one table (three launches in
+    training mode, two in eval mode).  Writes w[i] = w_orig[i] / sigma[i], sigma (n,), in training
+    mode u[i] / v[i] in place, and -- when ``saved`` is a flat tensor of sum(M + K) floats -- this
+    call's (u, v) of every layer into it, for the backward"""
+    n = len(w_orig)
+    if not (n and len(u) == len(v) == len(w) == len(dims) == n and sigma.numel() == n):
+        raise RuntimeError("sn_weight: one (w_orig, u, v, w, dim) per layer and one sigma each")
+    dev = w_orig[0].device
+    jobs, ws = _sn_table(w_orig, dims, dev)
+    _sn_check(w_orig, "weight_orig")
+    _sn_check(w, "weight", [t.numel() for t in w_orig])
+    _sn_check(u, "weight_u", [jb.M for jb in jobs])
+    _sn_check(v, "weight_v", [jb.K for jb in jobs])
+    _sn_check([sigma], "sigma")
+    total = sum(jb.M + jb.K for jb in jobs)
+    if saved.numel() not in (0, total):
+        raise RuntimeError(f"sn_weight: saved must hold {total} floats (or none)")
+    pos = saved.data_ptr()
+    for i, jb in enumerate(jobs):
+        jb.w_orig, jb.u, jb.v, jb.w = ptr(w_orig[i]), ptr(u[i]), ptr(v[i]), ptr(w[i])
+        jb.sigma = sigma.data_ptr() + 4 * i
+        if saved.numel():
+            jb.u_save, jb.v_save = pos, pos + 4 * jb.M
+            pos += 4 * (jb.M + jb.K)
+    nbytes = sum((12.0 if training else 8.0) * t.numel() + 4.0 * t.numel() for t in w_orig)
+    with rt.observe("sn_weight", bytes=nbytes):
+        check(rt.lib().ffc_sn_forward(jobs, n, 1 if training else 0, ptr(ws), ws.numel(), _stream(w_orig[0])),
+              "ffc_sn_forward")
+
+
+def sn_weight_bwd_impl(dw, w_orig, saved, sigma, dims):
+    """ffc::sn_weight_bwd -> [dw_orig]: dw / sigma - (<dw, w_orig> / sigma^2) u v^T per layer, (u, v) the
+    forward call's copies in ``saved``; two launches for the table"""
+    n = len(w_orig)
+    dev = w_orig[0].device
+    jobs, ws = _sn_table(w_orig, dims, dev)
+    dw = [g.contiguous() for g in dw]
+    _sn_check(w_orig, "weight_orig")
+    _sn_check(dw, "grad", [t.numel() for t in w_orig])
+    if saved.numel() != sum(jb.M + jb.K for jb in jobs) or sigma.numel() != n:
+        raise RuntimeError("sn_weight_bwd: saved / sigma do not match the layers")
+    out = [torch.empty_like(t) for t in w_orig]
+    pos = saved.data_ptr()
+    for i, jb in enumerate(jobs):
+        jb.w_orig, jb.dw, jb.dw_orig = ptr(w_orig[i]), ptr(dw[i]), ptr(out[i])
+        jb.u, jb.v = pos, pos + 4 * jb.M
+        pos += 4 * (jb.M + jb.K)
+        jb.sigma = sigma.data_ptr() + 4 * i
+    with rt.observe("sn_weight_bwd", bytes=sum(16.0 * t.numel() for t in w_orig)):
+        check(rt.lib().ffc_sn_backward(jobs, n, ptr(ws), ws.numel(), _stream(w_orig[0])), "ffc_sn_backward")
+    return out
+
+
+class SpectralNormWeight(torch.autograd.Function):
+    """SpectralNorm.compute_weight for a list of layers: (weight_orig...) -> (weight...).  ``layers`` is
+    [(weight_u, weight_v, dim)] -- buffers, constants for autograd as in the hook, advanced in place in
+    training mode.  Saves weight_orig, sigma and this call's (u, v) (the kernels' own copies: the
+    buffers move on at the next forward, which may come before this backward, the reason the hook
+    clones them).  Backward: ffc::sn_weight_bwd over the whole list."""
+
+    @staticmethod
+    def forward(ctx, layers, training, *w_orig):
+        src = [w.detach() for w in w_orig]
+        src = [s if s.is_contiguous() else s.contiguous() for s in src]
+        dims = [int(d) for _, _, d in layers]
+        out = [torch.empty_like(s) for s in src]
+        sigma = torch.empty(len(src), device=src[0].device, dtype=torch.float32)
+        need = any(ctx.needs_input_grad[2:])
+        saved = torch.empty(sum(u.numel() + v.numel() for u, v, _ in layers) if need else 0, device=src[0].device,
+                            dtype=torch.float32)
+        torch.ops.ffc.sn_weight(src, [u for u, _, _ in layers], [v for _, v, _ in layers], out, sigma, saved, dims,
+                                bool(training))
+        ctx.dims = dims
+        ctx.save_for_backward(saved, sigma, *src)
+        return tuple(out)
+
+    @staticmethod
+    def backward(ctx, *dws):
+        saved, sigma, *src = ctx.saved_tensors
+        dws = [g if g is not None else torch.zeros_like(s) for g, s in zip(dws, src)]
+        grads = torch.ops.ffc.sn_weight_bwd(dws, src, saved, sigma, ctx.dims)
+        return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))
+
+
+def sn_hook(mod):
+    """the module's SpectralNorm pre-hook when it is switched to the HIP path (set_sn_hip), else None"""
+    if not mod.__dict__.get("sn_hip"):
+        return None
+    from torch.nn.utils.spectral_norm import SpectralNorm
+    for h in mod._forward_pre_hooks.values():
+        if isinstance(h, SpectralNorm):
+            return h
+    return None
+
+
+def sn_weights(mods, hooks):
+    """refresh the spectral-norm weights of ``mods`` in one table: mod.<name> <- <name>_orig / sigma as a
+    differentiable function of <name>_orig (one power iteration each in training mode)"""
+    layers = [(getattr(m, h.name + "_u"), getattr(m, h.name + "_v"), h.dim) for m, h in zip(mods, hooks)]
+    modes = {bool(m.training) for m in mods}
+    if len(modes) != 1:
+        raise NotImplementedError("spectral norm: the layers of one table must share train / eval mode")
+    ws = SpectralNormWeight.apply(layers, modes.pop(), *[getattr(m, h.name + "_orig") for m, h in zip(mods, hooks)])
+    for m, h, w in zip(mods, hooks, ws):
+        setattr(m, h.name, w)

@@ -101,6 +101,14 @@ class CbnApplyItem(ctypes.Structure):
                 ("act_param", c_float), ("noise_w", c_void_p), ("noise", c_void_p)]
 
 
+class SnJob(ctypes.Structure):
+    """ffc_sn_job: one spectral-norm layer of ffc_sn_forward / ffc_sn_backward"""
+    _fields_ = [("w_orig", c_void_p), ("u", c_void_p), ("v", c_void_p), ("w", c_void_p), ("sigma", c_void_p),
+                ("u_save", c_void_p), ("v_save", c_void_p), ("dw", c_void_p), ("dw_orig", c_void_p),
+                ("M", c_int), ("K", c_int), ("R", c_int), ("pad_", c_int),
+                ("stride_m", c_longlong), ("stride_i", c_longlong), ("ws_off", c_longlong)]
+
+
 # (name, restype, argtypes) for every entry point declared in include/ffc_amd.h
 SIGNATURES = [
     ("ffc_last_error", ctypes.c_char_p, []),
@@ -250,6 +258,9 @@ SIGNATURES = [
     ("ffc_cbn_bwd_coeff", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     ("ffc_cbn_bwd_apply", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                   c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    ("ffc_sn_ws_bytes", c_size_t, [c_int, c_int]),
+    ("ffc_sn_forward", c_int, [ctypes.POINTER(SnJob), c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    ("ffc_sn_backward", c_int, [ctypes.POINTER(SnJob), c_int, c_void_p, c_size_t, c_void_p]),
 ]
 
 _lock = threading.Lock()
@@ -276,11 +287,12 @@ def load(path: str | None = None):
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        sizes = (c_int * 11)()
-        lib.ffc_struct_sizes(sizes, 11)
+        sizes = (c_int * 12)()
+        lib.ffc_struct_sizes(sizes, 12)
         want = (ctypes.sizeof(ConvSeg), ctypes.sizeof(ConvPhase), ctypes.sizeof(ConvJob),
                 ctypes.sizeof(ConvPSeg), ctypes.sizeof(ConvPPhase), ctypes.sizeof(ConvPJob), ctypes.sizeof(BnFold),
-                ctypes.sizeof(InTf), ctypes.sizeof(BnRfItem), ctypes.sizeof(BnApplyItem), ctypes.sizeof(CbnApplyItem))
+                ctypes.sizeof(InTf), ctypes.sizeof(BnRfItem), ctypes.sizeof(BnApplyItem), ctypes.sizeof(CbnApplyItem),
+                ctypes.sizeof(SnJob))
         if tuple(sizes) != want:
             raise FFCError(f"ABI struct layout mismatch: library {tuple(sizes)} vs binding {want}")
         _lib = lib

@@ -1043,9 +1043,13 @@ def sn_refresh(mod):
     """Run a module's torch.nn.utils.spectral_norm pre-hook (W <- W_orig / sigma, with one power
     iteration in training mode) at the point where the reference's forward would call the module
     (layers/snffc/snffc.py:23-33); the HIP path reads module.weight without calling the module.
-    The power iteration stays host-driven PyTorch, as in the reference."""
+    By default the power iteration stays host-driven PyTorch, as in the reference; a
+    module switched on by set_sn_hip runs it, sigma and the division on the ffc::sn_weight op, written
+    straight into the persistent tensor."""
     hooks = getattr(mod, "_forward_pre_hooks", None)
     if not hooks:
+        return
+    if mod.__dict__.get("sn_hip") and _sn_refresh_hip(mod):
         return
     from torch.nn.utils.spectral_norm import SpectralNorm
     for h in hooks.values():
@@ -1063,12 +1067,72 @@ def sn_refresh(mod):
             setattr(mod, h.name, buf)
 
 
+def _sn_refresh_hip(mod):
+    """sn_refresh on the HIP path: no autograd, W lands in the persistent tensor (its version moves, so
+    the packed-weight caches repack).  False when the module has no SpectralNorm hook"""
+    from . import _autograd as ag
+    h = ag.sn_hook(mod)
+    if h is None:
+        return False
+    w_orig = getattr(mod, h.name + "_orig").detach()
+    buf = mod.__dict__.get("_ffc_sn_" + h.name)
+    if buf is None or buf.shape != w_orig.shape or buf.device != w_orig.device or not buf.is_contiguous():
+        buf = torch.empty(w_orig.shape, device=w_orig.device, dtype=w_orig.dtype)
+        mod.__dict__["_ffc_sn_" + h.name] = buf
+    sigma = torch.empty(1, device=w_orig.device, dtype=torch.float32)
+    with torch.no_grad():
+        torch.ops.ffc.sn_weight([w_orig.contiguous()], [getattr(mod, h.name + "_u")], [getattr(mod, h.name + "_v")],
+                                [buf], sigma, sigma.new_empty(0), [int(h.dim)], bool(mod.training))
+    setattr(mod, h.name, buf)
+    return True
+
+
+_SN_BATCHED = set()   # ids of the modules a model forward has refreshed in its own table (sn_batch)
+
+
+class sn_batch:
+    """``with sn_batch(mods):`` refreshes the spectral-norm weights of those of ``mods`` that are switched
+    to the HIP path (set_sn_hip) in ONE table -- three launches forward, two backward, whatever the
+    number of layers -- and turns their per-layer sn_refresh_train calls inside the block into no-ops:
+    one power iteration per layer and forward call, as the reference's module calls do (power
+    iterations do not depend on activations, so refreshing up front changes no result).  Modules
+    without the switch are left to their per-layer refresh."""
+
+    def __init__(self, mods):
+        self.mods = mods
+        self.ids = ()
+
+    def __enter__(self):
+        from . import _autograd as ag
+        pairs = [(m, ag.sn_hook(m)) for m in self.mods if m.__dict__.get("sn_hip") and id(m) not in _SN_BATCHED]
+        pairs = [(m, h) for m, h in pairs if h is not None]
+        if pairs:
+            ag.sn_weights([m for m, _ in pairs], [h for _, h in pairs])
+            self.ids = tuple(id(m) for m, _ in pairs)
+            _SN_BATCHED.update(self.ids)
+        return self
+
+    def __exit__(self, *exc):
+        _SN_BATCHED.difference_update(self.ids)
+        return False
+
+
 def sn_refresh_train(mod):
     """training path: run the spectral_norm pre-hooks so ``mod.weight`` = weight_orig / sigma is a
-    differentiable function of weight_orig (the reference calls the module, which does the same)"""
+    differentiable function of weight_orig (the reference calls the module, which does the same).
+    With set_sn_hip: the ffc::sn_weight op with a table of one, or nothing when the model refreshed
+    this module in its own table at the top of the forward (sn_batch)"""
     hooks = getattr(mod, "_forward_pre_hooks", None)
     if not hooks:
         return
+    if mod.__dict__.get("sn_hip"):
+        if id(mod) in _SN_BATCHED:
+            return
+        from . import _autograd as ag
+        h = ag.sn_hook(mod)
+        if h is not None:
+            ag.sn_weights([mod], [h])
+            return
     from torch.nn.utils.spectral_norm import SpectralNorm
     for h in hooks.values():
         if isinstance(h, SpectralNorm):

@@ -70,5 +70,6 @@ extern "C" int ffc_struct_sizes(int* out, int n) {
         out[9] = (int)sizeof(ffc_bn_apply_item);
     }
     if (n >= 11) out[10] = (int)sizeof(ffc_cbn_apply_item);
+    if (n >= 12) out[11] = (int)sizeof(ffc_sn_job);
     return FFC_OK;
 }

@@ -4,7 +4,8 @@
 they are Conv2d) and the Conv2d children of the SpectralTransform (conv1, conv2) -- exactly the
 reference's wrapping.  The HIP executor refreshes each normalised weight (one power iteration in
 training mode, host-driven PyTorch as in the reference) where the reference's forward would call the
-module (_runtime.sn_refresh), so the packed GEMM weights always see W / sigma.
+module (_runtime.sn_refresh), so the packed GEMM weights always see W / sigma.  ``set_sn_hip`` moves
+the power iteration, sigma and the division onto the HIP kernels of csrc/sn_kernels.hip (off by default).
 
 ``SNFFCTranspose`` reproduces the reference constructor, including its defect: it wraps
 ``self.convg2gup``, which FFCTranspose never defines (snffc_transpose.py:28), so construction raises
@@ -12,6 +13,7 @@ AttributeError exactly as the reference does.  ``spectral_norm_ffc`` applies the
 reference intended to any FFC / FFCTranspose stack (BASELINE config 5: the fgan128 generator with
 spectral norm on l2l / l2g / g2l and the SpectralTransform conv1 / conv2).
 """
+import torch
 import torch.nn as nn
 from torch.nn.utils import spectral_norm
 
@@ -85,4 +87,46 @@ def set_mix_precision(model: nn.Module, precision: str) -> nn.Module:
     for m in model.modules():
         if isinstance(m, FourierUnitSN):
             m.mix_precision = precision
+    return model
+
+
+def set_sn_hip(model: nn.Module, on: bool = True) -> nn.Module:
+    """Run the spectral norm of every ``torch.nn.utils.spectral_norm``-wrapped module in ``model`` on the
+    HIP kernels (ffc::sn_weight: power iteration, sigma and W = W_orig / sigma in three launches, sigma
+    never leaving the device) instead of the hook's host-driven ATen ops; ``on=False`` returns to the
+    hook, with weight_u / weight_v where the HIP path left them.  Off by default.  The hook object stays
+    registered and the state_dict keys (weight_orig, weight_u, weight_v) are unchanged.  Discriminator
+    and its subclasses then refresh all their layers in one table per forward.  Raises
+    NotImplementedError, naming the module, for n_power_iterations != 1, a weight that is not fp32 and
+    a parametrization-style (torch.nn.utils.parametrizations) spectral norm.  Returns ``model``."""
+    from torch.nn.utils.spectral_norm import SpectralNorm
+    marked = []
+    for name, m in model.named_modules():
+        label = name or type(m).__name__
+        par = getattr(m, "parametrizations", None)
+        if on and par is not None:
+            for plist in par.values():
+                if any(type(p).__name__ == "_SpectralNorm" for p in plist):
+                    raise NotImplementedError(f"set_sn_hip: {label} uses torch.nn.utils.parametrizations."
+                                              "spectral_norm (other buffers and clone semantics); wrap it with "
+                                              "torch.nn.utils.spectral_norm")
+        hooks = [h for h in m._forward_pre_hooks.values() if isinstance(h, SpectralNorm)]
+        if not hooks:
+            continue
+        if on:
+            if len(hooks) != 1:
+                raise NotImplementedError(f"set_sn_hip: {label} has {len(hooks)} spectral norms; one is supported")
+            h = hooks[0]
+            if h.n_power_iterations != 1:
+                raise NotImplementedError(f"set_sn_hip: {label} has n_power_iterations = {h.n_power_iterations}; "
+                                          "the HIP path runs one power iteration per forward")
+            w = getattr(m, h.name + "_orig")
+            if w.dtype != torch.float32:
+                raise NotImplementedError(f"set_sn_hip: {label}.{h.name}_orig is {w.dtype}; fp32 only")
+            if h.dim not in (0, 1) or w.dim() < 2:
+                raise NotImplementedError(f"set_sn_hip: {label}: spectral norm over dim {h.dim} of a "
+                                          f"{w.dim()}-d weight")
+        marked.append(m)
+    for m in marked:   # nothing is switched when any module was refused
+        m.sn_hip = bool(on)
     return model

@@ -242,12 +242,16 @@ class Discriminator(FFCModel):
             raise RuntimeError(f"{type(self).__name__}: x must be (B, 3, {side}, {side}), got {tuple(x.shape)}")
         act, param = rt.act_code(self.act)
         m = x
-        for i in range(1, len(self.CONVS) + 1):
-            conv = getattr(self, f"conv{i}")
-            B, C, H, W = m.shape
-            sg = _plan.Seg("conv", C, H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
-            (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)], [(0, 0, sg, conv)], [m])
-        return ag.linear(self.fc, m.reshape(m.shape[0], -1))   # :556
+        with rt.sn_batch(self._sn_layers()):   # set_sn_hip: conv1..convN and fc in one table
+            for i in range(1, len(self.CONVS) + 1):
+                conv = getattr(self, f"conv{i}")
+                B, C, H, W = m.shape
+                sg = _plan.Seg("conv", C, H, W, conv.kernel_size[0], conv.stride[0], conv.padding[0])
+                (m,) = ag.conv_layer(B, [(conv.out_channels, act, param)], [(0, 0, sg, conv)], [m])
+            return ag.linear(self.fc, m.reshape(m.shape[0], -1))   # :556
+
+    def _sn_layers(self):
+        return [getattr(self, f"conv{i}") for i in range(1, len(self.CONVS) + 1)] + [self.fc]
 
 
 FGanDiscriminator = Discriminator
@@ -405,6 +409,11 @@ def _label_plane_critic(self, x, labels, side):
     """the label-conditioned plain critic on a (B, 3, side, side) image: label_embed's row of each sample's
     class as a fourth input plane of conv1, then conv2.. and fc (fgan128_cond_complete.py:159-178,
     fgan_cond_complete.py:211-227)"""
+    with rt.sn_batch(self._sn_layers()):   # set_sn_hip: conv1..convN and fc in one table
+        return _label_plane_critic_body(self, x, labels, side)
+
+
+def _label_plane_critic_body(self, x, labels, side):
     B = x.shape[0]
     act, param = rt.act_code(self.act)
     plane = torch.ops.ffc.embed_rows(self.label_embed.weight, labels).view(B, 1, side, side)

@@ -564,6 +564,36 @@ def _cbn_act_bwd(ctx, grads):
 
 cbn_act.register_autograd(_cbn_act_bwd, setup_context=_cbn_act_setup)
 
+# ---------------------------------------------------------------- ffc::sn_weight
+# torch.nn.utils.spectral_norm's pre-hook (one power iteration, sigma, W = W_orig / sigma) for a list
+# of layers on csrc/sn_kernels.hip; the autograd wrapper is _autograd.SpectralNormWeight
+
+
+@torch.library.custom_op("ffc::sn_weight", mutates_args=("u", "v", "w", "sigma", "saved"))
+def sn_weight(w_orig: List[Tensor], u: List[Tensor], v: List[Tensor], w: List[Tensor], sigma: Tensor, saved: Tensor,
+              dims: List[int], training: bool) -> None:
+    """w[i] <- w_orig[i] / sigma[i]; training: u[i], v[i] advanced in place by one power iteration;
+    saved: a flat copy of this call's (u, v) per layer, or an empty tensor"""
+    ag.sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training)
+
+
+@sn_weight.register_fake
+def _(w_orig, u, v, w, sigma, saved, dims, training):
+    return None
+
+
+@torch.library.custom_op("ffc::sn_weight_bwd", mutates_args=())
+def sn_weight_bwd(dw: List[Tensor], w_orig: List[Tensor], saved: Tensor, sigma: Tensor,
+                  dims: List[int]) -> List[Tensor]:
+    """-> [dw_orig]: dw / sigma - (<dw, w_orig> / sigma^2) u v^T per layer"""
+    return ag.sn_weight_bwd_impl(dw, w_orig, saved, sigma, dims)
+
+
+@sn_weight_bwd.register_fake
+def _(dw, w_orig, saved, sigma, dims):
+    return [t.new_empty(t.shape) for t in w_orig]
+
+
 # =========================================================================== inference ops
 
 

@@ -43,7 +43,7 @@ int ffc_abi_version(void);
 /* sizeof(ffc_conv_seg), (ffc_conv_phase), (ffc_conv_job), (ffc_convp_seg), (ffc_convp_phase),
  * (ffc_convp_job) -> out[0..5]; n >= 7: sizeof(ffc_bn_fold) -> out[6]; n >= 8: sizeof(ffc_in_tf) -> out[7];
  * n >= 10: sizeof(ffc_bn_rf_item), sizeof(ffc_bn_apply_item) -> out[8], out[9];
- * n >= 11: sizeof(ffc_cbn_apply_item) -> out[10] */
+ * n >= 11: sizeof(ffc_cbn_apply_item) -> out[10]; n >= 12: sizeof(ffc_sn_job) -> out[11] */
 int ffc_struct_sizes(int* out, int n);
 
 /* ------------------------------------------------------------------ local branch
@@ -734,6 +734,48 @@ int ffc_cbn_bwd_coeff(const float* sums, const int64_t* labels, const float* emb
 int ffc_cbn_bwd_apply(const float* x, const float* dy, const int64_t* labels, const float* embed, int B, int C,
                       int HW, int num_classes, const float* scale0, const float* shift0, int act, float act_param,
                       const float* coef, float* dx, void* stream);
+
+/* ------------------------------------------------------------------ spectral norm
+ * torch.nn.utils.spectral_norm's pre-hook (SpectralNorm.compute_weight, n_power_iterations = 1) for
+ * a table of n >= 1 layers in the same launches.  Per layer, with the weight seen as a matrix
+ * Wm (M x K) and normalize(x) = x / max(||x||_2, 1e-12):
+ *   training:  v <- normalize(Wm^T u),  u <- normalize(Wm v),  sigma = u . (Wm v),  W = W_orig / sigma
+ *   eval:      sigma = u . (Wm v) from the stored vectors,  W = W_orig / sigma   (u, v not written)
+ * The matrix view is read in place through (R, stride_m, stride_i):
+ *   Wm[m][k] = w_orig[(k / R) * stride_i + m * stride_m + k % R]
+ *   dim = 0 (Conv2d, Linear):            R = K,       stride_m = K, stride_i = 0
+ *   dim = 1 (ConvTranspose2d (in, out, kh, kw)): R = kh * kw, stride_m = R, stride_i = M * R, K = in * R
+ * (these two dense forms are the ones accepted).  W, dw and dw_orig have w_orig's layout, elementwise.
+ * Three launches in training mode (column sums of Wm^T u split over rows and columns; Wm p with
+ * p = Wm^T u rebuilt from the partial columns -- the division by ||p|| commutes with the product and is
+ * applied to the M results; normalise + scale), two in eval mode.  Every partial sum has a fixed
+ * place and the merges run in a fixed order in fp64: no atomics, bitwise reproducible, and a layer's
+ * results do not depend on what else is in the table.  sigma stays on the device.
+ * Workspace: ffc_sn_ws_bytes(M, K) bytes per layer at byte offset ws_off (a multiple of 16) of ws;
+ * 0 for M, K <= 0 or M * K >= 2^31.  16-byte accesses when R % 4 == 0 (rows) / the tensors are 16-byte
+ * aligned (elementwise passes), 4-byte otherwise.  Pure additions: the ABI version is unchanged. */
+typedef struct ffc_sn_job {
+    const float* w_orig;   /* M * K floats */
+    float* u;              /* (M): read; written in training mode */
+    float* v;              /* (K): written in training mode, read in eval mode */
+    float* w;              /* forward output, != w_orig */
+    float* sigma;          /* one float: written by the forward, read by the backward */
+    float* u_save;         /* forward: optional copies of this call's u / v (both or neither), */
+    float* v_save;         /*          for a backward that runs after a later refresh */
+    const float* dw;       /* backward only */
+    float* dw_orig;        /* backward only */
+    int M, K;
+    int R;
+    int pad_;
+    long long stride_m, stride_i;
+    long long ws_off;
+} ffc_sn_job;
+size_t ffc_sn_ws_bytes(int M, int K);
+int ffc_sn_forward(const ffc_sn_job* jobs, int n, int training, void* ws, size_t ws_bytes, void* stream);
+/* dw_orig = dw / sigma - (<dw, w_orig> / sigma^2) * u v^T  (u, v constants, as in the hook): partials
+ * of <dw, w_orig> per 16384-element chunk in fp64, merged in order; two launches for the table.  u, v,
+ * sigma: what the forward of the same call left (u_save / v_save when given). */
+int ffc_sn_backward(const ffc_sn_job* jobs, int n, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
