@@ -722,17 +722,33 @@ extern "C" int ffc_bn_reduce_finalize_batch(const ffc_bn_rf_item* items, int n, 
 extern "C" int ffc_bn_act_apply_batch(const ffc_bn_apply_item* items, int n, void* stream) {
     FFC_CHECK_ARG(items && n >= 1 && n <= FFC_MAX_BN_BATCH, "ffc_bn_act_apply_batch: 1 <= n <= 4 items");
     ApplyBatch a = {};
+    const auto aligned = [](const ffc_bn_apply_item& t) {
+        return ((reinterpret_cast<uintptr_t>(t.x) | reinterpret_cast<uintptr_t>(t.y) |
+                 reinterpret_cast<uintptr_t>(t.noise)) & 15) == 0;
+    };
+    const auto is_plane = [&](const ffc_bn_apply_item& t) { return t.HW % 4 == 0 && t.HW >= 256 && aligned(t); };
+    // every item is validated before the first launch (the callers apply in place: a batch rejected
+    // half way would leave a half-applied layer behind)
     long long blocks = 0;
     for (int i = 0; i < n; ++i) {
         const ffc_bn_apply_item& t = items[i];
         FFC_CHECK_ARG(t.x && t.y && t.scale && t.shift && t.B > 0 && t.C > 0 && t.HW > 0,
                       "ffc_bn_act_apply_batch: bad item");
         FFC_CHECK_ARG(!t.noise || t.noise_w, "ffc_bn_act_apply_batch: noise needs noise_w");
-        const bool plane = t.HW % 4 == 0 && t.HW >= 256 &&
-                           ((reinterpret_cast<uintptr_t>(t.x) | reinterpret_cast<uintptr_t>(t.y) |
-                             reinterpret_cast<uintptr_t>(t.noise)) & 15) == 0;
+        const bool plane = is_plane(t);
         FFC_CHECK_ARG(plane || !t.plane_sum, "ffc_bn_act_apply_batch: plane_sum needs HW % 4 == 0, HW >= 256, aligned");
-        if (!plane) {   // the single forms' other paths
+        // what ffc_bn_act_noise_apply would reject below
+        FFC_CHECK_ARG(plane || !t.noise || (t.HW % 4 == 0 && aligned(t)),
+                      "ffc_bn_act_apply_batch: noise needs H*W % 4 == 0 and 16-byte aligned tensors");
+        if (plane) {
+            blocks += (long long)t.B * t.C * ((t.HW / 4 + PLANE_CHUNK4 - 1) / PLANE_CHUNK4);
+            FFC_CHECK_ARG(blocks < (1LL << 31), "ffc_bn_act_apply_batch: grid too large");
+        }
+    }
+    blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const ffc_bn_apply_item& t = items[i];
+        if (!is_plane(t)) {   // the single forms' other paths
             const int rc = t.noise ? ffc_bn_act_noise_apply(t.x, t.y, t.B, t.C, t.HW, t.scale, t.shift, t.act,
                                                             t.act_param, t.noise_w, t.noise, stream)
                                    : ffc_bn_act_apply(t.x, t.y, t.B, t.C, t.HW, t.scale, t.shift, t.act, t.act_param,
@@ -755,7 +771,6 @@ extern "C" int ffc_bn_act_apply_batch(const ffc_bn_apply_item* items, int n, voi
         a.p[k] = t.act_param;
         a.off[k] = (int)blocks;
         blocks += (long long)t.B * t.C * a.chunks[k];
-        FFC_CHECK_ARG(blocks < (1LL << 31), "ffc_bn_act_apply_batch: grid too large");
     }
     if (a.n == 0) return FFC_OK;
     a.off[a.n] = (int)blocks;

@@ -259,7 +259,8 @@ int ffc_bn_act_noise_apply(const float* x, float* y, int B, int C, int HW, const
 /* Batched forms for the BNs of one FFC layer (bn_l and bn_g come out of the same conv launch,
  * ffc_bn_act.py:80-83): up to FFC_MAX_BN_BATCH items per call, one launch for all of them where the
  * single forms would launch once per item (launch latency dominates these small kernels).  Each item
- * has the meaning of the single call's arguments. */
+ * has the meaning of the single call's arguments.  Every item is validated before the first launch:
+ * a batch that returns FFC_E_INVALID has written nothing, to no item's outputs. */
 #define FFC_MAX_BN_BATCH 4
 typedef struct ffc_bn_rf_item {       /* ffc_bn_reduce_finalize arguments */
     const float* slab;
