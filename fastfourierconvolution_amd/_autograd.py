@@ -113,70 +113,23 @@ def run_conv(cache, key, B, M, segs, weights, inputs, out_shape=None, act=(0, 0.
     return out
 
 
-def smallm_route(segs, layouts, M):
-    """<= 4 output channels: 'full' (Conv2d onto a 1x1 output, ffc_conv_full_smallm), 'convT'
-    (ConvTranspose2d k4 s2 p1, ffc_convt_k4s2_smallm), else None (implicit-GEMM kernels)"""
-    if M > 4 or not 1 <= len(segs) <= 2 or not rt.USE_SMALLM:
-        return None
-    if all(sg.kind == "conv" and sg.k == sg.IH == sg.IW and sg.p == 0 and sg.d == 1 and not sg.pool and not sg.gate
-           for sg in segs) and all(lay == 0 for lay in layouts):
-        return "full"
-    if all(sg.kind == "convT" and (sg.k, sg.s, sg.p, sg.d, sg.op) == (4, 2, 1, 1, 0) for sg in segs) and \
-            all((sg.IH, sg.IW) == (segs[0].IH, segs[0].IW) for sg in segs) and sum(sg.C for sg in segs) <= 256 and \
-            all(lay == 1 for lay in layouts):
-        return "convT"
-    return None
-
-
 def conv_forward(cache, key, B, M, segs, weights, inputs, out_shape=None, act=(0, 0.0), addend=None):
-    """out = act(sum_s conv_s(x_s) [+ addend]) on the best kernel for the job: the small-M direct
-    kernels for <= 4 output channels, the implicit-GEMM kernels otherwise"""
-    route = None
-    if addend is None and sum(1 for w in weights if w[4] is not None) <= 1:
-        route = smallm_route(segs, [w[1] for w in weights], M)
-    if route is None and addend is None and len(segs) == 1 and weights[0][4] is None and weights[0][1] == 1:
-        sg = segs[0]
-        if sg.kind == "convT" and (sg.IH, sg.IW, sg.s, sg.p, sg.d, sg.op) == (1, 1, 1, 0, 1, 0) and sg.C <= 256:
-            # ConvTranspose2d on a 1x1 input (FFCGenerator ffc0, models/ffc_generator.py:24): a plain GEMM
-            # out (B, M*k*k) = x (B, C) . W (C, M*k*k) on the dense kernel; W needs no packing
-            Wt = weights[0][0]
-            N = M * sg.k * sg.k
-            out = torch.empty((B, M, sg.k, sg.k), device=inputs[0].device, dtype=torch.float32)
-            with rt.observe("dense", flops=2.0 * B * sg.C * N):
-                check(rt.lib().ffc_dense_forward(ptr(inputs[0]), ptr(Wt), None, B, sg.C, N, N, ptr(out), None,
-                                                 act[0], float(act[1]), _stream(out)), "ffc_dense_forward")
-            return out
+    """out = act(sum_s conv_s(x_s) [+ addend]) on the kernel rt.conv_route picks for the training path: a
+    direct kernel (small M; ConvTranspose2d on a 1x1 input), the implicit-GEMM kernels otherwise"""
+    weights = rt.conv_weights(weights)
+    route = rt.conv_route(segs, weights, M, addend is not None, False, rt.TRAIN_ROUTES, training=True)
     if route is None:
         return run_conv(cache, key, B, M, segs, weights, inputs, out_shape, act, addend)
-    L = rt.lib()
-    bias = next((w[4] for w in weights if w[4] is not None), None)
-    x1 = inputs[1] if len(inputs) > 1 else None
-    w1 = weights[1][0] if len(weights) > 1 else None
-    dev = inputs[0].device
     stream = _stream(inputs[0])
-    if route == "full":
+    if route == "dense":
+        # FFCGenerator ffc0 (models/ffc_generator.py:24): W (C, M, k, k) is the GEMM's (K, N) as it stands
         sg = segs[0]
-        out = torch.empty((B, M, 1, 1), device=dev, dtype=torch.float32)
-        K0 = sg.C * sg.k * sg.k
-        K1 = segs[1].C * segs[1].k * segs[1].k if x1 is not None else 0
-        with rt.observe("conv_full_smallm", flops=2.0 * B * M * (K0 + K1)):
-            check(L.ffc_conv_full_smallm(ptr(inputs[0]), K0, ptr(weights[0][0]), ptr(x1), K1, ptr(w1), ptr(bias), B, M,
-                                         ptr(out), act[0], float(act[1]), stream), "ffc_conv_full_smallm")
+        N = M * sg.k * sg.k
+        out = torch.empty((B, M, sg.k, sg.k), device=inputs[0].device, dtype=torch.float32)
+        rt.dense_forward(inputs[0], weights[0].w, None, B, sg.C, N, N, out, None, act, stream)
         return out
-    C0, C1 = segs[0].C, (segs[1].C if x1 is not None else 0)
-    pkey = ("ctpack", key, rt.weight_key(weights[0][0]), rt.weight_key(w1))
-    wp = cache.get(pkey)
-    if wp is None:
-        for old in [k for k in cache if k[:2] == ("ctpack", key)]:
-            del cache[old]
-        wp = cache[pkey] = torch.empty(L.ffc_convt_smallm_pack_floats(C0, C1), device=dev, dtype=torch.float32)
-        check(L.ffc_convt_smallm_pack(ptr(weights[0][0]), C0, ptr(w1), C1, M, ptr(wp), stream), "ffc_convt_smallm_pack")
-    IH, IW = segs[0].IH, segs[0].IW
-    out = torch.empty((B, M, 2 * IH, 2 * IW), device=dev, dtype=torch.float32)
-    with rt.observe("convt_smallm", flops=2.0 * B * M * (C0 + C1) * 4 * (2 * IH) * (2 * IW)):
-        check(L.ffc_convt_k4s2_smallm(ptr(inputs[0]), C0, ptr(x1), C1, ptr(wp), ptr(bias), B, IH, IW, M, ptr(out),
-                                      act[0], float(act[1]), stream), "ffc_convt_k4s2_smallm")
-    return out
+    # the packed convT weights in one slot per job: under spectral norm W / sigma is a new tensor every step
+    return rt.smallm_forward(route, segs, weights, inputs, M, B, act, stream, rt.packs_of(cache), pack_slot=key)
 
 
 def wgrad_splits(B, Mu, NT, P, bt=64):
@@ -278,8 +231,8 @@ def conv_layer_impl(xs, ws, bs, spec):
     for j, (M, act, param) in enumerate(outs_s):
         es = [e for e in range(len(edges)) if edges[e][0] == j]
         sgs = tuple(segs[e] for e in es)
-        wts = [(ws[e], edges[e][8], edges[e][3], edges[e][3], bs[edges[e][9]] if edges[e][9] >= 0 else None)
-               for e in es]
+        wts = [rt.ConvWeight(ws[e], edges[e][8], edges[e][3], edges[e][3],
+                             bs[edges[e][9]] if edges[e][9] >= 0 else None) for e in es]
         fused = act if act != 5 else 0
         with _CL_POOL.hold() as cache:
             y = conv_forward(cache, ("fwd", spec, j, B, sgs), B, M, sgs, wts, [xs[edges[e][1]] for e in es],
@@ -327,7 +280,7 @@ def conv_layer_backward_impl(xs, ws, ts, gouts, needs, spec):
         dx = None
         for grp in groups:
             segs = tuple(a[1] for a in grp)
-            wts = [(ws[a[0]].contiguous(), 1 - a[2], a[1].k, a[1].k, None) for a in grp]
+            wts = [rt.ConvWeight(ws[a[0]].contiguous(), 1 - a[2], a[1].k, a[1].k, None) for a in grp]
             key = ("adj", spec, i, tuple(a[0] for a in grp), B, C, segs)
             with _CL_POOL.hold() as cache:
                 dx = conv_forward(cache, key, B, C, segs, wts, [a[3] for a in grp], out_shape=tuple(x.shape),

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -196,24 +197,33 @@ def _bn_finalize_batch(items, batch, device, stream):
             for it in items]
 
 
+class ActApply(NamedTuple):
+    """one tensor of bn_act_apply_batch: x <- act(scale * x + shift) (+ noise_w * noise), in place"""
+    x: torch.Tensor
+    scale: torch.Tensor
+    shift: torch.Tensor
+    act: int
+    param: float
+    noise_w: Optional[torch.Tensor] = None
+    noise: Optional[torch.Tensor] = None
+    plane_sums: Optional[torch.Tensor] = None   # (B, C, ffc_plane_chunks(HW)): receives the chunk sums of y
+
+
 def bn_act_apply_batch(items):
-    """[(x, scale, shift, act, param, noise_w or None, noise or None[, plane_sum or None])]: y = x in
-    place, one launch (ffc_bn_act_apply_batch; the l and g outputs of an FFC_BN_ACT, with fgan128's
-    NoiseInjection).  plane_sum (B, C, ffc_plane_chunks(HW)) receives the chunk sums of y."""
+    """[ActApply] in one launch (ffc_bn_act_apply_batch; the l and g outputs of an FFC_BN_ACT, with
+    fgan128's NoiseInjection)"""
     from ._lib import BnApplyItem
     arr = (BnApplyItem * len(items))()
     nbytes = 0.0
     for k, it in enumerate(items):
-        x, sc, sh, act, param, nw, nz = it[:7]
-        ps = it[7] if len(it) > 7 else None
-        B, C = x.shape[:2]
-        HW = x.numel() // (B * C)
-        arr[k] = BnApplyItem(ptr(x), ptr(x), B, C, HW, ptr(sc), ptr(sh), int(act), float(param), ptr(nw), ptr(nz),
-                             ptr(ps))
-        nbytes += 8.0 * x.numel() + (4.0 * nz.numel() if nz is not None else 0.0)
-    label = "bn_act_noise" if any(it[6] is not None for it in items) else "bn_act"
+        B, C = it.x.shape[:2]
+        HW = it.x.numel() // (B * C)
+        arr[k] = BnApplyItem(ptr(it.x), ptr(it.x), B, C, HW, ptr(it.scale), ptr(it.shift), int(it.act),
+                             float(it.param), ptr(it.noise_w), ptr(it.noise), ptr(it.plane_sums))
+        nbytes += 8.0 * it.x.numel() + (4.0 * it.noise.numel() if it.noise is not None else 0.0)
+    label = "bn_act_noise" if any(it.noise is not None for it in items) else "bn_act"
     with observe(label, bytes=nbytes):
-        check(lib().ffc_bn_act_apply_batch(arr, len(items), stream_of(items[0][0])), "ffc_bn_act_apply_batch")
+        check(lib().ffc_bn_act_apply_batch(arr, len(items), stream_of(items[0].x)), "ffc_bn_act_apply_batch")
 
 
 def bn_scale_shift_many(items, device, stream):
@@ -659,19 +669,34 @@ class StreamPool:
 
 
 class PackCache:
-    """a few packed forms of weights, keyed by weight_key of their sources (FIFO-bounded)"""
+    """Forms derived from weights (packed, transposed, concatenated).  An entry lives in a slot and holds
+    the weight_key of the sources it was built from; sources with another key (a new version, or a new
+    tensor object: another epoch) re-build into the same slot, so nothing stale stays behind.  The slot is
+    (tag, the sources' pointers): an updated weight, and a new tensor at a freed one's address, replace
+    the old entry, while other models' weights get slots of their own.  A caller whose source is a fresh
+    tensor every step, possibly at a new address (W / sigma on the training path), names the slot itself
+    (``slot``: its job key).  Slots are FIFO-bounded by ``cap``."""
 
     def __init__(self, cap: int = 16):
         self.cap, self.d = cap, {}
 
-    def get(self, tag, sources, build):
-        key = (tag,) + _wkey(sources)
-        v = self.d.get(key)
-        if v is None:
-            if len(self.d) >= self.cap:
+    def get(self, tag, sources, build, slot=None):
+        key = _wkey(sources)
+        slot = (tag, slot if slot is not None else tuple(None if k is None else k[0] for k in key))
+        hit = self.d.get(slot)
+        if hit is None or hit[0] != key:
+            if hit is None and len(self.d) >= self.cap:
                 self.d.pop(next(iter(self.d)))
-            v = self.d[key] = build()
-        return v
+            hit = self.d[slot] = (key, build())
+        return hit[1]
+
+
+def packs_of(cache: dict) -> PackCache:
+    """the PackCache kept inside a plan cache (a layer's executor cache, the conv_layer op's)"""
+    p = cache.get("packs")
+    if p is None:
+        p = cache["packs"] = PackCache(64)
+    return p
 
 
 # --------------------------------------------------------------------------- convolution jobs
@@ -739,8 +764,8 @@ PRESPLIT_A = _env("FFC_CONVP_PRESPLIT", "0", lambda s: s == "1")   # A/B knob: A
 # persistent grid (r03) reversed that (tools/convq_probe.py)
 USE_CONVQ = _env("FFC_CONVQ", "auto", _not0)
 CONVQ_FORCE = _env("FFC_CONVQ", "auto", lambda s: s in ("1", "force"))
-USE_OUTER = True   # ConvT on a 1x1 input as one outer-product GEMM (ffc._FFCExec._outer_rewrite)
-USE_SMALLM = True  # direct VALU ConvT for <= 4 output channels (ffc_convt_k4s2_smallm)
+USE_OUTER = True   # inference: ConvT on a 1x1 input as one outer-product GEMM (conv_route, _FFCExec._outer_rewrite)
+USE_SMALLM = True  # direct VALU kernels for <= 4 output channels (conv_route 'convT' / 'full' / 'conv3')
 FORCE_FU2D = False  # large-plane FU stages even where the fused per-sample FU applies (tests)
 # SpectralTransform prologue: "auto" = the fused per-sample kernel where the sample fits in LDS
 # (st_prologue.hip), else SE gate + gated 1x1 GEMM (st_pw.hip); "pw" forces the latter (A/B runs)
@@ -777,6 +802,127 @@ def side_stream(device):
     return s
 
 
+class ConvWeight(NamedTuple):
+    """one segment's weight: layout 0 = (M, C, kh, kw) (nn.Conv2d), 1 = (C, M, kh, kw) (nn.ConvTranspose2d)"""
+    w: torch.Tensor
+    layout: int
+    kh: int
+    kw: int
+    bias: Optional[torch.Tensor]
+
+
+def conv_weights(weights):
+    """-> [ConvWeight]; callers outside the package may pass plain (w, layout, kh, kw, bias) tuples"""
+    return [w if isinstance(w, ConvWeight) else ConvWeight(*w) for w in weights]
+
+
+# ----- the route of a convolution job: a direct kernel, or the implicit-GEMM kernels
+class RouteCaps:
+    """channel caps of the direct kernels: their argument checks refuse more, so conv_route never sends it
+    (constants of the kernels, not switches: tests/test_route_cpu.py compares them with the sources)"""
+    CONVT_SMALLM_CMAX = 256   # CT_CMAX in csrc/convt_smallm.hip (ffc_convt_k4s2_smallm: both segments' channels)
+    CONV3_SMALLM_CMAX = 256   # CMAX3 in csrc/convt_smallm.hip (ffc_conv3x3_smallm: both segments' channels)
+    DENSE_KMAX = 256          # DN_KMAX in csrc/dense.hip (ffc_dense_forward: the A tile's K staged in LDS)
+
+
+INFER_ROUTES = frozenset(("convT", "full", "conv3", "dense"))
+# _autograd.conv_forward has never sent a job to the 3x3 kernel (its 3x3 jobs run on the implicit-GEMM
+# kernels); that answer is kept
+TRAIN_ROUTES = frozenset(("convT", "full", "dense"))
+
+
+def conv_route(segs, weights, M, has_addend, has_bn, accept, training=False):
+    """The kernel for out = act(sum_s conv_s(x_s)) with M output channels and ConvWeight ``weights``, among
+    the routes the caller accepts.  Looks at shapes only (no tensor data, no device).
+    -> None: the implicit-GEMM kernels, or
+      'convT'  <= 4 output channels, ConvTranspose2d k4 s2 p1 (the generator's last layer): ffc_convt_k4s2_smallm
+      'full'   <= 4 output channels, Conv2d onto a 1x1 output (FFCDiscriminator's last layer): ffc_conv_full_smallm
+      'conv3'  <= 4 output channels, Conv2d k3 s1 p1 on rows of 4n pixels (the fgan128 head): ffc_conv3x3_smallm
+      'dense'  ConvTranspose2d(k, s=1, p=0) on a 1x1 input (the generators' first layer), a plain GEMM
+               out (B, M k k) = x (B, C) . W (C, M k k): ffc_dense_forward
+    No direct kernel adds an addend, collects BN partials, pools or gates its input, or takes two biases.
+    ``training`` marks the two points where the callers' launchers differ (below)."""
+    if has_addend or has_bn or M is None or not segs or any(sg.pool or sg.gate for sg in segs):
+        return None
+    layouts = {w.layout for w in weights}
+    C = sum(sg.C for sg in segs)
+    one_plane = all((sg.IH, sg.IW) == (segs[0].IH, segs[0].IW) for sg in segs)
+    route = None
+    if USE_SMALLM and M <= 4 and len(segs) <= 2 and sum(w.bias is not None for w in weights) <= 1:
+        if all(sg.kind == "convT" and (sg.k, sg.s, sg.p, sg.d, sg.op) == (4, 2, 1, 1, 0) for sg in segs):
+            if one_plane and layouts == {1} and C <= RouteCaps.CONVT_SMALLM_CMAX:
+                route = "convT"
+        elif all(sg.kind == "conv" and sg.k == sg.IH == sg.IW and sg.p == 0 and sg.d == 1 for sg in segs):
+            # segments of two plane sizes: the kernel takes them (K0, K1) and the training path sends them;
+            # the inference executor never did (one kernel size per layer: it cannot meet them).  Both kept
+            if layouts == {0} and (one_plane or training):
+                route = "full"
+        elif all(sg.kind == "conv" and (sg.k, sg.s, sg.p, sg.d) == (3, 1, 1, 1) for sg in segs):
+            if one_plane and segs[0].IW % 4 == 0 and C <= RouteCaps.CONV3_SMALLM_CMAX:
+                route = "conv3"
+    sg = segs[0]
+    if route is None and len(segs) == 1 and sg.kind == "convT" and layouts == {1} and C <= RouteCaps.DENSE_KMAX and \
+            (sg.IH, sg.IW, sg.s, sg.p, sg.d, sg.op) == (1, 1, 1, 0, 1, 0):
+        # inference repeats the bias over the k x k taps (_FFCExec._outer_rewrite) and honours USE_OUTER;
+        # the training launcher passes W as it is, so it takes bias-free jobs only, and it never looked
+        # at USE_OUTER (a switch of the inference executor's rewrite): each caller's answer is kept
+        if (weights[0].bias is None) if training else USE_OUTER:
+            route = "dense"
+    return route if route in accept else None
+
+
+def smallm_forward(route, segs, weights, xs, M, B, act, stream, packs=None, pack_slot=None, tfs=None):
+    """launch the direct kernel of a 'convT' / 'full' / 'conv3' job (conv_route) -> out.
+    packs, pack_slot: the PackCache (and its slot, see there) for the convT kernel's packed weights;
+    tfs: per input, the PendingAct whose
+    BN + activation (+ noise) the 3x3 kernel applies as it stages that input (or None)"""
+    L = lib()
+    dev = xs[0].device
+    x1 = xs[1] if len(xs) > 1 else None
+    w0, w1 = weights[0].w, (weights[1].w if len(weights) > 1 else None)
+    bias = next((w.bias for w in weights if w.bias is not None), None)
+    C0, C1 = segs[0].C, (segs[1].C if x1 is not None else 0)
+    IH, IW = segs[0].IH, segs[0].IW
+    a, ap = act[0], float(act[1])
+    if route == "full":
+        out = torch.empty((B, M, 1, 1), device=dev, dtype=torch.float32)
+        K0 = C0 * segs[0].k * segs[0].k
+        K1 = C1 * segs[1].k * segs[1].k if x1 is not None else 0
+        with observe("conv_full_smallm", flops=2.0 * B * M * (K0 + K1)):
+            check(L.ffc_conv_full_smallm(ptr(xs[0]), K0, ptr(w0), ptr(x1), K1, ptr(w1), ptr(bias), B, M, ptr(out),
+                                         a, ap, stream), "ffc_conv_full_smallm")
+        return out
+    if route == "convT":
+        def pack():   # [C0 + C1][16 taps][4] by a HIP kernel
+            wp = torch.empty(L.ffc_convt_smallm_pack_floats(C0, C1), device=dev, dtype=torch.float32)
+            check(L.ffc_convt_smallm_pack(ptr(w0), C0, ptr(w1), C1, M, ptr(wp), stream), "ffc_convt_smallm_pack")
+            return wp
+        wp = packs.get("ctpack", [w0, w1], pack, slot=pack_slot)
+        out = torch.empty((B, M, 2 * IH, 2 * IW), device=dev, dtype=torch.float32)
+        with observe("convt_smallm", flops=2.0 * B * M * (C0 + C1) * 4 * (2 * IH) * (2 * IW)):
+            check(L.ffc_convt_k4s2_smallm(ptr(xs[0]), C0, ptr(x1), C1, ptr(wp), ptr(bias), B, IH, IW, M, ptr(out),
+                                          a, ap, stream), "ffc_convt_k4s2_smallm")
+        return out
+    out = torch.empty((B, M, IH, IW), device=dev, dtype=torch.float32)
+    head = (ptr(xs[0]), C0, ptr(w0), ptr(x1), C1, ptr(w1), ptr(bias), B, IH, IW, M, ptr(out), a, ap)
+    with observe("conv3_smallm", flops=2.0 * B * M * (C0 + C1) * 9 * IH * IW):
+        if tfs is not None and any(t is not None for t in tfs):
+            st = [t.struct() if t is not None else None for t in tfs] + [None]
+            check(L.ffc_conv3x3_smallm_tf(*head, None if st[0] is None else ctypes.byref(st[0]),
+                                          None if st[1] is None else ctypes.byref(st[1]), stream),
+                  "ffc_conv3x3_smallm_tf")
+        else:
+            check(L.ffc_conv3x3_smallm(*head, stream), "ffc_conv3x3_smallm")
+    return out
+
+
+def dense_forward(x, Wt, bias, B, K, N, N0, out0, out1, act, stream):
+    """ffc_dense_forward: act(x (B, K) . Wt (K, N) + bias), columns [0, N0) to out0 and the rest to out1"""
+    with observe("dense", flops=2.0 * B * K * N):
+        check(lib().ffc_dense_forward(ptr(x), ptr(Wt), ptr(bias), B, K, N, N0, ptr(out0), ptr(out1), act[0],
+                                      float(act[1]), stream), "ffc_dense_forward")
+
+
 class ConvExec:
     """One planned + packed job: output = sum of segment convolutions of fixed shapes.
 
@@ -784,6 +930,7 @@ class ConvExec:
     kind 'gemm'  -> ffc_conv_forward (generic phase GEMM with gathered B)."""
 
     def __init__(self, B, M, segs, weights, device, pw_ok=False, convq_cfg=None):
+        weights = conv_weights(weights)
         pw_only = all(sg.kind == "pw" and not sg.pool and not sg.gate for sg in segs)
         pp = (_plan.pick_patch_cfg(B, M, segs, 128 if CONV_ARITH == "split" else 512)
               if USE_PATCH and not (pw_only and PW_KERNEL == "gemm") else None)
@@ -810,7 +957,7 @@ class ConvExec:
         # pack, so the kernel loads the pieces instead of splitting each chunk's A in registers
         self.a3_stride = -(-self.a_floats // 8) * 8
         self.use_a3 = self.kind == "patch" and CONV_ARITH == "split" and (PRESPLIT_A or self.plan.q)
-        self.has_bias = any(w[4] is not None for w in weights)
+        self.has_bias = any(w.bias is not None for w in weights)
         self.M = M
         # packed buffers per weight identity: modules of one structure share this plan,
         # and alternating them must neither re-pack every call nor overwrite a buffer in use
@@ -914,7 +1061,8 @@ class ConvExec:
         return job
 
     def ensure_packed(self, weights):
-        key = _wkey([w[0] for w in weights] + [w[4] for w in weights])
+        weights = conv_weights(weights)
+        key = _wkey([w.w for w in weights] + [w.bias for w in weights])
         if key == self._packed:
             return
         # identity = the weight objects (pointer, epoch) without their versions: an updated weight
@@ -936,11 +1084,11 @@ class ConvExec:
         self._slots[ident] = (key,) + tuple(bufs)
         n = len(weights)
         job = self.pack_job()
-        wp = (ctypes.c_void_p * _lib.MAX_SEG)(*[w[0].data_ptr() for w in weights], *([None] * (_lib.MAX_SEG - n)))
-        lay = (ctypes.c_int * _lib.MAX_SEG)(*[w[1] for w in weights], *([0] * (_lib.MAX_SEG - n)))
-        kh = (ctypes.c_int * _lib.MAX_SEG)(*[w[2] for w in weights], *([1] * (_lib.MAX_SEG - n)))
-        kw = (ctypes.c_int * _lib.MAX_SEG)(*[w[3] for w in weights], *([1] * (_lib.MAX_SEG - n)))
-        bp = (ctypes.c_void_p * _lib.MAX_SEG)(*[ptr(w[4]) for w in weights], *([None] * (_lib.MAX_SEG - n)))
+        wp = (ctypes.c_void_p * _lib.MAX_SEG)(*[w.w.data_ptr() for w in weights], *([None] * (_lib.MAX_SEG - n)))
+        lay = (ctypes.c_int * _lib.MAX_SEG)(*[w.layout for w in weights], *([0] * (_lib.MAX_SEG - n)))
+        kh = (ctypes.c_int * _lib.MAX_SEG)(*[w.kh for w in weights], *([1] * (_lib.MAX_SEG - n)))
+        kw = (ctypes.c_int * _lib.MAX_SEG)(*[w.kw for w in weights], *([1] * (_lib.MAX_SEG - n)))
+        bp = (ctypes.c_void_p * _lib.MAX_SEG)(*[ptr(w.bias) for w in weights], *([None] * (_lib.MAX_SEG - n)))
         check(lib().ffc_conv_pack(ctypes.byref(job), wp, lay, kh, kw, bp, self.A.data_ptr(),
                                   ptr(self.bias), torch.cuda.current_stream(self.device).cuda_stream),
               "ffc_conv_pack")
@@ -1140,12 +1288,12 @@ def sn_refresh_train(mod):
 
 
 def conv_weight(mod):
-    """(weight, layout, kh, kw, bias) for nn.Conv2d (layout 0) / nn.ConvTranspose2d (layout 1)."""
+    """ConvWeight of an nn.Conv2d (layout 0) / nn.ConvTranspose2d (layout 1)."""
     w = mod.weight.detach()
     kh, kw = w.shape[2], w.shape[3]
     b = mod.bias.detach() if mod.bias is not None else None
-    return (require(w, "weight"), 1 if isinstance(mod, nn.ConvTranspose2d) else 0, kh, kw,
-            require(b, "bias") if b is not None else None)
+    return ConvWeight(require(w, "weight"), 1 if isinstance(mod, nn.ConvTranspose2d) else 0, kh, kw,
+                      require(b, "bias") if b is not None else None)
 
 
 def _square(v, what):

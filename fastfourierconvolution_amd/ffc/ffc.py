@@ -11,7 +11,8 @@ with the FFC_BN_ACT activation fused into the epilogue (or BN partials, then one
 BN+activation pass when norm_layer is BatchNorm2d).  ``nn.Identity`` sub-convs keep the
 reference semantics: they return their input (usually the int 0 of the tuple protocol).
 """
-import ctypes
+from dataclasses import dataclass
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -23,14 +24,67 @@ from .. import ops
 from .spectral_transform import SpectralTransform
 
 
+class Branch(NamedTuple):
+    """one output branch of a layer: out = act(BN(sum_s conv_s(inputs[s]) + addends))"""
+    name: str          # "l" | "g"
+    segs: list         # _plan.Seg per convolution
+    weights: list      # rt.ConvWeight per convolution
+    inputs: list       # input tensor per convolution
+    addends: list      # tensors passed through nn.Identity sub-convs
+    act: tuple         # (code, parameter)
+    bn: Optional[nn.Module]
+    M: Optional[int]   # output channels (None: no convolution)
+
+
+@dataclass(slots=True)
+class _Job:
+    """a branch planned on the implicit-GEMM kernels (its segments possibly in the outer-product form)"""
+    branch: Branch
+    key: tuple         # of ``ex`` in the layer's cache
+    ex: rt.ConvExec
+    segs: list
+    weights: list
+    M: int
+    out: torch.Tensor
+    addend: Optional[torch.Tensor]
+
+
+class _Dense(NamedTuple):
+    """an outer-product branch for ffc_dense_forward: weight (N, C, 1, 1) with its bias repeated over the taps"""
+    weight: rt.ConvWeight   # derived by _outer_rewrite from ...
+    source: rt.ConvWeight   # ... the module's own weight and bias (what the launch's pack is keyed on)
+    x: torch.Tensor
+    out: torch.Tensor
+    act: tuple
+    N: int
+
+
+class _Post(NamedTuple):
+    """an output that still needs its BN and / or activation (+ noise) pass"""
+    name: str
+    out: torch.Tensor
+    act: tuple
+    bn: Optional[nn.Module]
+    slab: Optional[torch.Tensor]   # BN partials from the GEMM epilogue
+    nrows: int
+
+
+def _is_conv(mod):
+    return isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d))
+
+
+def _no_conditional():
+    # the reference passes y into SpectralTransform / FourierUnitSN, whose BatchNorm2d.forward()
+    # takes no label (fourier_unity.py:46-47), or into nn.Identity.forward (one argument)
+    raise TypeError("FFC: the conditional (y) path is not supported (the reference raises in "
+                    "FourierUnitSN, fourier_unity.py:46-47)")
+
+
 def layer_call(mod, ffc, x, y, act_l=(0, 0.0), act_g=(0, 0.0), bn_l=None, bn_g=None, noise=None, defer=False):
     """forward of FFC_BN_ACT / FFC / FFCTranspose ``mod`` whose FFC part is ``ffc``: the training ops
     when autograd needs them, else the fused ffc::ffc_bn_act op"""
     if y is not None and ffc.ratio_gout != 0:
-        # the reference passes y into SpectralTransform / FourierUnitSN, whose BatchNorm2d.forward()
-        # takes no label (fourier_unity.py:46-47), or into nn.Identity.forward (one argument)
-        raise TypeError("FFC: the conditional (y) path is not supported (the reference raises in "
-                        "FourierUnitSN, fourier_unity.py:46-47)")
+        _no_conditional()
     x_l, x_g = x if type(x) is tuple else (x, 0)
     if ag.wants_grad(mod, x_l, x_g):
         x_l, x_g = rt.materialize(x_l), rt.materialize(x_g)
@@ -51,19 +105,34 @@ class _FFCExec:
         """parts: list of (module, input) whose outputs are summed.  -> (segments, weights, inputs, addends)"""
         segs, weights, inputs, addends = [], [], [], []
         for mod, inp in parts:
-            if isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d)):
+            if _is_conv(mod):
                 if not isinstance(inp, torch.Tensor):
                     raise TypeError(f"{type(mod).__name__} got {type(inp).__name__} input")
                 rt.sn_refresh(mod)
                 segs.append(rt.conv_seg(mod, inp))
                 weights.append(rt.conv_weight(mod))
-                inputs.append((inp, None))
+                inputs.append(inp)
             elif isinstance(mod, nn.Identity):
                 if isinstance(inp, torch.Tensor):
                     addends.append(inp)       # Identity passes a tensor through
             else:
                 raise NotImplementedError(f"{type(mod).__name__} in an FFC branch")
         return segs, weights, inputs, addends
+
+    def _g_branch(self, x_l, spectral_v, act_g, bn_g):
+        """the global output branch convl2g(x_l) + conv2(v) as one job; spectral_v() -> v = s + fu(s), the
+        SpectralTransform up to its conv2 (None without one).  It is called after convl2g's weight is
+        taken, where the one-stream path has always run the spectral chain."""
+        segs, w, inp, add = self._branch([(self.convl2g, x_l)])
+        M = self.convl2g.out_channels if _is_conv(self.convl2g) else None
+        if spectral_v is not None:
+            v, conv2 = spectral_v(), self.convg2g.conv2
+            rt.sn_refresh(conv2)
+            segs.append(_plan.Seg("pw", v.shape[1], v.shape[2], v.shape[3]))
+            w.append(rt.conv_weight(conv2))
+            inp.append(v)
+            M = conv2.out_channels if M is None else M
+        return Branch("g", segs, w, inp, add, act_g, bn_g, M)
 
     def _run(self, x, y=None, act_l=(0, 0.0), act_g=(0, 0.0), bn_l=None, bn_g=None, noise=None, defer=False):
         """noise: optional {"l"|"g": (NoiseInjection, noise tensor or None)} applied after the branch's
@@ -87,15 +156,19 @@ class _FFCExec:
             raise TypeError("FFC input has no tensor branch")
         B, dev = ref.shape[0], ref.device
         stream = rt.stream_of(ref)
-        branches = []  # (name, segs, weights, inputs, addends, act, bn, M)
+        branches = []
         if self.ratio_gout != 1:
             segs, w, inp, add = self._branch([(self.convl2l, x_l), (self.convg2l, x_g)])
-            M = self.convl2l.out_channels if isinstance(self.convl2l, (nn.Conv2d, nn.ConvTranspose2d)) else (
-                self.convg2l.out_channels if isinstance(self.convg2l, (nn.Conv2d, nn.ConvTranspose2d)) else None)
-            branches.append(("l", segs, w, inp, add, act_l, bn_l, M))
-        spectral = (self.ratio_gout != 0 and isinstance(self.convg2g, SpectralTransform) and y is None and
-                    isinstance(x_g, torch.Tensor))
-        if rt.OVERLAP_SPECTRAL and spectral and branches and branches[0][1]:
+            M = next((m.out_channels for m in (self.convl2l, self.convg2l) if _is_conv(m)), None)
+            branches.append(Branch("l", segs, w, inp, add, act_l, bn_l, M))
+        if self.ratio_gout == 0:
+            return self._launch_branches(branches, B, dev, stream, noise, defer)
+        st = self.convg2g
+        if not isinstance(st, (nn.Identity, SpectralTransform)):
+            raise NotImplementedError(type(st).__name__)
+        spectral = isinstance(st, SpectralTransform)
+        if rt.OVERLAP_SPECTRAL and spectral and y is None and isinstance(x_g, torch.Tensor) and branches and \
+                branches[0].segs:
             # The local branch does not depend on the spectral chain: its GEMM runs on the main stream
             # while SpectralTransform's latency-bound kernels run on a side stream (fork / join by
             # events, hipGraph-capturable); then the global-branch GEMM consumes v.
@@ -104,43 +177,24 @@ class _FFCExec:
             side.wait_stream(main)
             if rt.OVERLAP_SPECTRAL == "spectral-first":
                 with torch.cuda.stream(side):
-                    v = self.convg2g.spectral(x_g)
+                    v = st.spectral(x_g)
                 out_l, _ = self._launch_branches(branches, B, dev, stream, noise)
             else:
                 out_l, _ = self._launch_branches(branches, B, dev, stream, noise)
                 with torch.cuda.stream(side):
-                    v = self.convg2g.spectral(x_g)
+                    v = st.spectral(x_g)
             main.wait_stream(side)
             v.record_stream(main)
-            segs, w, inp, add = self._branch([(self.convl2g, x_l)])
-            rt.sn_refresh(self.convg2g.conv2)
-            segs.append(_plan.Seg("pw", v.shape[1], v.shape[2], v.shape[3]))
-            w.append(rt.conv_weight(self.convg2g.conv2))
-            inp.append((v, None))
-            M = self.convl2g.out_channels if isinstance(self.convl2g, (nn.Conv2d, nn.ConvTranspose2d)) else \
-                self.convg2g.conv2.out_channels
-            _, out_g = self._launch_branches([("g", segs, w, inp, add, act_g, bn_g, M)], B, dev, stream, noise)
+            _, out_g = self._launch_branches([self._g_branch(x_l, lambda: v, act_g, bn_g)], B, dev, stream, noise)
             return out_l, out_g
-        if self.ratio_gout != 0:
-            segs, w, inp, add = self._branch([(self.convl2g, x_l)])
-            if not isinstance(self.convg2g, nn.Identity):
-                if isinstance(self.convg2g, SpectralTransform):
-                    if y is not None:
-                        raise TypeError("FFC: the conditional (y) path is not supported (the reference raises in "
-                                        "FourierUnitSN, fourier_unity.py:46-47)")
-                    if not isinstance(x_g, torch.Tensor):
-                        raise TypeError("spectral branch needs a tensor x_g")
-                    v = self.convg2g.spectral(x_g)
-                    st = self.convg2g
-                    rt.sn_refresh(st.conv2)
-                    segs.append(_plan.Seg("pw", v.shape[1], v.shape[2], v.shape[3]))
-                    w.append(rt.conv_weight(st.conv2))
-                    inp.append((v, None))
-                else:
-                    raise NotImplementedError(type(self.convg2g).__name__)
-            M = self.convl2g.out_channels if isinstance(self.convl2g, (nn.Conv2d, nn.ConvTranspose2d)) else (
-                self.convg2g.conv2.out_channels if isinstance(self.convg2g, SpectralTransform) else None)
-            branches.append(("g", segs, w, inp, add, act_g, bn_g, M))
+
+        def spectral_v():
+            if y is not None:
+                _no_conditional()
+            if not isinstance(x_g, torch.Tensor):
+                raise TypeError("spectral branch needs a tensor x_g")
+            return st.spectral(x_g)
+        branches.append(self._g_branch(x_l, spectral_v if spectral else None, act_g, bn_g))
         return self._launch_branches(branches, B, dev, stream, noise, defer)
 
     def _run_pending(self, x_l, x_g, y, act_l, act_g, bn_l, bn_g, noise):
@@ -152,13 +206,12 @@ class _FFCExec:
         if not all(isinstance(m, nn.Conv2d) and isinstance(t, (torch.Tensor, rt.PendingAct)) for m, t in parts):
             return None
         raw = [t.raw if isinstance(t, rt.PendingAct) else rt.require(t, "x") for _, t in parts]
-        segs, w, inp, add = self._branch([(m, r) for (m, _), r in zip(parts, raw)])
+        segs, w, inp, _ = self._branch([(m, r) for (m, _), r in zip(parts, raw)])
         M = self.convl2l.out_channels
-        if self._smallm_kind(segs, w, None, None, M) != "conv3":
+        if rt.conv_route(segs, w, M, False, False, frozenset(("conv3",))) != "conv3":
             return None
         tfs = [t if isinstance(t, rt.PendingAct) else None for _, t in parts]
-        return self._smallm("conv3", segs, w, inp, act_l, M, raw[0].shape[0], raw[0].device,
-                            rt.stream_of(raw[0]), tfs=tfs), 0
+        return rt.smallm_forward("conv3", segs, w, inp, M, raw[0].shape[0], act_l, rt.stream_of(raw[0]), tfs=tfs), 0
 
     def _run_train(self, x_l, x_g, y, act_l, act_g, bn_l, bn_g, noise):
         """training path (autograd recording): the layer's local convs and ST conv2 as one
@@ -166,8 +219,7 @@ class _FFCExec:
         SpectralTransform through its per-op Functions, BN + activation as _BNActFn
         (include/ffc_amd.h "training path")."""
         if y is not None:
-            raise TypeError("FFC: the conditional (y) path is not supported (the reference raises in "
-                            "FourierUnitSN, fourier_unity.py:46-47)")
+            _no_conditional()
         for t, n in ((x_l, "x_l"), (x_g, "x_g")):
             if isinstance(t, torch.Tensor):
                 rt.require(t, n)
@@ -186,7 +238,7 @@ class _FFCExec:
         def branch(parts, extra=None):
             convs = []
             for mod, t in parts:
-                if isinstance(mod, (nn.Conv2d, nn.ConvTranspose2d)):
+                if _is_conv(mod):
                     if not isinstance(t, torch.Tensor):
                         raise TypeError(f"{type(mod).__name__} got {type(t).__name__} input")
                     convs.append((mod, t))
@@ -227,45 +279,47 @@ class _FFCExec:
         return res["l"], res["g"]
 
     def _launch_branches(self, branches, B, dev, stream, noise=None, defer=False):
-        """plan / pack / launch the GEMM(s) of the given branches (one launch per kernel kind),
+        """route, plan / pack and launch the GEMM(s) of the given branches (one launch per kernel kind),
         then BN statistics and BN+activation passes (defer: PendingAct outputs instead of those
         passes).  -> (out_l, out_g)"""
         outs = {"l": 0, "g": 0}
-        execs, jobs, post, built = [], [], [], []
-        jb_name = {}
-        dense = []   # (name, (W (M', C, 1, 1), layout, 1, 1, bias), input, out, act, M')
-        for name, segs, w, inp, add, act, bn, M in branches:
-            if len(add) > 1:
-                raise NotImplementedError("more than one identity pass-through in a branch")
-            addend = add[0] if add else None
-            if not segs:
+        if any(len(br.addends) > 1 for br in branches):
+            raise NotImplementedError("more than one identity pass-through in a branch")
+        routes = [rt.conv_route(br.segs, br.weights, br.M, bool(br.addends), br.bn is not None, rt.INFER_ROUTES)
+                  for br in branches]
+        jobs, post = self._plan_branches(branches, routes, B, dev, stream, outs)
+        self._launch_jobs(jobs, dev, stream, post)
+        self._finish(post, outs, noise or {}, defer, dev, stream)
+        return outs["l"], outs["g"]
+
+    def _plan_branches(self, branches, routes, B, dev, stream, outs):
+        """per branch, in order: its pass-through copy, its direct kernel (launched here), or its plan,
+        packed weights and output on the implicit-GEMM kernels.  -> (jobs, post)"""
+        cache = self._ffc_cache()
+        jobs, post, dense = [], [], []
+        for br, route in zip(branches, routes):
+            addend = br.addends[0] if br.addends else None
+            if not br.segs:
                 # no convolution: the branch is its pass-through (or the int 0)
-                if addend is None:
-                    continue
-                out = addend.clone()
-                outs[name] = out
-                post.append((name, out, act, bn, None, 0))
+                if addend is not None:
+                    outs[br.name] = addend.clone()
+                    post.append(_Post(br.name, outs[br.name], br.act, br.bn, None, 0))
                 continue
-            smk = self._smallm_kind(segs, w, addend, bn, M)
-            if smk is not None:
-                out = self._smallm(smk, segs, w, inp, act, M, B, dev, stream)
-                outs[name] = out
+            if route in ("convT", "full", "conv3"):
+                outs[br.name] = rt.smallm_forward(route, br.segs, br.weights, br.inputs, br.M, B, br.act, stream,
+                                                  rt.packs_of(cache))
                 continue
-            out_shape = None
-            if addend is None and bn is None:
-                rw = self._outer_rewrite(segs, w, M)
-                if rw is not None and len(segs) == 1:
+            segs, w, M, out_shape = br.segs, br.weights, br.M, None
+            rw = self._outer_rewrite(segs, w, M) if addend is None and br.bn is None else None
+            if rw is not None:
+                segs, w, M, chw = rw
+                out_shape = (B,) + chw
+                if route == "dense":
                     # a plain GEMM: batched with the other branch's into one dense launch below
-                    segs2, w2, M2, chw = rw
-                    out = torch.empty((B,) + chw, device=dev, dtype=torch.float32)
-                    outs[name] = out
-                    dense.append((name, w2[0], inp[0][0], out, act, M2))
+                    outs[br.name] = torch.empty(out_shape, device=dev, dtype=torch.float32)
+                    dense.append(_Dense(w[0], br.weights[0], br.inputs[0], outs[br.name], br.act, M))
                     continue
-                if rw is not None:
-                    segs, w, M, chw = rw
-                    out_shape = (B,) + chw
-            key = (name, B, tuple(segs), str(dev))
-            cache = self._ffc_cache()
+            key = (br.name, B, tuple(segs), str(dev))
             ex = cache.get(key)
             if ex is None:
                 ex = cache[key] = rt.ConvExec(B, M, segs, w, dev)
@@ -274,92 +328,98 @@ class _FFCExec:
             out = torch.empty(out_shape or (B, pl.M, pl.OH, pl.OW), device=dev, dtype=torch.float32)
             if addend is not None and tuple(addend.shape) != tuple(out.shape):
                 raise RuntimeError(f"shape mismatch adding pass-through {tuple(addend.shape)} to {tuple(out.shape)}")
-            outs[name] = out
-            jb_name[id(out)] = name
-            execs.append(ex)
-            jobs.append((ex, inp, out, act, bn, addend))
-            built.append((key, B, M, segs, w))
+            outs[br.name] = out
+            jobs.append(_Job(br, key, ex, segs, w, M, out, addend))
         if dense:
             self._launch_dense(dense, B, stream)
         # the layer's convq jobs share one launch, so one configuration: when they picked different
         # ones (untuned shapes), rebuild them on the costliest job's (cached: happens once)
-        qi = [i for i, jb in enumerate(jobs) if jb[0].launch_key[0] == "q"]
-        if len({jobs[i][0].launch_key for i in qi}) > 1:
+        qjobs = [jb for jb in jobs if jb.ex.launch_key[0] == "q"]
+        if len({jb.ex.launch_key for jb in qjobs}) > 1:
             # the decision is cached per layer shape, including "this job cannot take that cfg" (it
             # stays on its own kernel): nothing is re-planned or re-packed on later forwards
-            cache = self._ffc_cache()
-            rkey = ("rebuild",) + tuple(built[i][0] for i in qi)
+            rkey = ("rebuild",) + tuple(jb.key for jb in qjobs)
             dec = cache.get(rkey)
             if dec is None:
-                cfg = max((jobs[i][0].plan for i in qi), key=_plan.convq_cost).cfg
+                cfg = max((jb.ex.plan for jb in qjobs), key=_plan.convq_cost).cfg
                 dec = {}
-                for i in qi:
-                    ckey, cB, cM, csegs, cw = built[i]
-                    ex2 = rt.ConvExec(cB, cM, csegs, cw, dev, convq_cfg=cfg)
+                for i, jb in enumerate(qjobs):
+                    ex2 = rt.ConvExec(B, jb.M, jb.segs, jb.weights, dev, convq_cfg=cfg)
                     if ex2.launch_key[0] == "q":
-                        cache[ckey] = dec[i] = ex2
+                        cache[jb.key] = dec[i] = ex2
                 cache[rkey] = dec
             for i, ex2 in dec.items():
-                ex2.ensure_packed(built[i][4])
-                jobs[i] = (ex2,) + jobs[i][1:]
+                ex2.ensure_packed(qjobs[i].weights)
+                qjobs[i].ex = ex2
+        return jobs, post
+
+    def _launch_jobs(self, jobs, dev, stream, post):
+        """one launch per kernel configuration; a job with a BN gets its slab of partials and a post item"""
+        cache = self._ffc_cache()
         groups = {}
         for jb in jobs:
-            groups.setdefault(jb[0].launch_key, []).append(jb)
-        cache = self._ffc_cache()
+            groups.setdefault(jb.ex.launch_key, []).append(jb)
         for gjobs in groups.values():
-            lkey = ("launch",) + tuple(id(j[0]) for j in gjobs)
+            lkey = ("launch",) + tuple(id(jb.ex) for jb in gjobs)
             lp = cache.get(lkey)
             if lp is None:
-                lp = cache[lkey] = rt.LaunchPlan([j[0] for j in gjobs], dev)
+                lp = cache[lkey] = rt.LaunchPlan([jb.ex for jb in gjobs], dev)
             structs = []
-            for ji, (ex, inp, out, act, bn, addend) in enumerate(gjobs):
+            for ji, jb in enumerate(gjobs):
+                act, bn = jb.branch.act, jb.branch.bn
                 slab = None
                 if bn is not None and rt.bn_mode(bn)[0]:
-                    slab = torch.empty((lp.stat_rows(ji), ex.plan.M, 4), device=dev, dtype=torch.float32)
+                    slab = torch.empty((lp.stat_rows(ji), jb.ex.plan.M, 4), device=dev, dtype=torch.float32)
                 fused_act = act if bn is None else (0, 0.0)
-                structs.append(ex.job(inp, out, fused_act[0], fused_act[1], addend, slab))
+                structs.append(jb.ex.job([(x, None) for x in jb.branch.inputs], jb.out, fused_act[0], fused_act[1],
+                                         jb.addend, slab))
                 if bn is not None:
-                    post.append((jb_name[id(out)], out, act, bn, slab, lp.stat_rows(ji)))
-            lp.launch(structs, stream, flops=sum(j[0].flops for j in gjobs))
-        noise = noise or {}
+                    post.append(_Post(jb.branch.name, jb.out, act, bn, slab, lp.stat_rows(ji)))
+            lp.launch(structs, stream, flops=sum(jb.ex.flops for jb in gjobs))
+
+    def _finish(self, post, outs, noise, defer, dev, stream):
+        """BN scale / shift of the post items, then their BN + activation (+ noise) passes as one launch
+        (defer: rt.PendingAct outputs instead); a NoiseInjection without such a pass runs on its own"""
         done = set()
         applies = []
         # the layer's slab-backed BNs (bn_l, bn_g) finalized together: one SyncBN all-reduce for both
-        slab_bns = [(bn, out.shape[1], slab, nrows, 1.0) for _, out, _, bn, slab, nrows in post
-                    if bn is not None and slab is not None]
+        slab_bns = [(it.bn, it.out.shape[1], it.slab, it.nrows, 1.0) for it in post
+                    if it.bn is not None and it.slab is not None]
         ss = dict(zip((id(it[0]) for it in slab_bns), rt.bn_scale_shift_many(slab_bns, dev, stream)))
-        for name, out, act, bn, slab, nrows in post:
+        for it in post:
+            out, (act, param) = it.out, it.act
             C = out.shape[1]
-            nz = noise.get(name)
-            if bn is not None:
-                if slab is not None:
-                    sc, sh = ss[id(bn)]
+            nz = noise.get(it.name)
+            if it.bn is not None:
+                if it.slab is not None:
+                    sc, sh = ss[id(it.bn)]
+                elif rt.bn_mode(it.bn)[0]:
+                    sc, sh = self._bn_from_tensor(it.bn, out, stream)
                 else:
-                    sc, sh = rt.bn_scale_shift(bn, C, slab, nrows, 1.0, dev, stream) if not rt.bn_mode(bn)[0] \
-                        else self._bn_from_tensor(bn, out, stream)
+                    sc, sh = rt.bn_scale_shift(it.bn, C, None, it.nrows, 1.0, dev, stream)
             else:
-                if act[0] == 0 and nz is None:
+                if act == 0 and nz is None:
                     continue
                 sc = torch.ones(C, device=dev, dtype=torch.float32)
                 sh = torch.zeros(C, device=dev, dtype=torch.float32)
             if defer:
-                outs[name] = rt.PendingAct(out, sc, sh, act[0], act[1], *(nz if nz is not None else (None, None)))
-                done.add(name)
+                outs[it.name] = rt.PendingAct(out, sc, sh, act, param, *(nz if nz is not None else (None, None)))
+                done.add(it.name)
                 continue
             # the global output's plane sums for the next layer's SE gate (large planes, where the
             # SpectralTransform reads y twice otherwise: spectral_transform.py pw path)
             HW = out.shape[2] * out.shape[3]
             ps = None
-            if name == "g" and rt.SE_SUMS and HW % 4 == 0 and HW >= 256:
+            if it.name == "g" and rt.SE_SUMS and HW % 4 == 0 and HW >= 256:
                 chunks = rt.lib().ffc_plane_chunks(HW)
                 ps = torch.empty((out.shape[0], out.shape[1], chunks), device=dev, dtype=torch.float32)
             if nz is not None and HW % 4 == 0:
                 # the noise drawn here, in branch order, as the single pass does; applied below
-                p = rt.PendingAct(out, sc, sh, act[0], act[1], *nz)
-                applies.append((out, sc, sh, act[0], act[1], p.noise_w, p.noise, ps))
-                done.add(name)
+                p = rt.PendingAct(out, sc, sh, act, param, *nz)
+                applies.append(rt.ActApply(out, sc, sh, act, param, p.noise_w, p.noise, ps))
+                done.add(it.name)
             else:
-                applies.append((out, sc, sh, act[0], act[1], None, None, ps))
+                applies.append(rt.ActApply(out, sc, sh, act, param, plane_sums=ps))
             if ps is not None:
                 out._ffc_plane_sums = (ps, chunks, out._version)
         if applies:   # the layer's BN + activation (+ noise) passes in one launch
@@ -367,136 +427,59 @@ class _FFCExec:
         for name, (mod, n) in noise.items():   # branches without a BN/activation pass of their own
             if name not in done and isinstance(outs[name], torch.Tensor):
                 outs[name] = mod(outs[name], n)
-        return outs["l"], outs["g"]
 
     def _outer_rewrite(self, segs, w, M):
         """ConvTranspose2d(k, s=1, p=0) on a 1x1 input (the generator's first layer, ffc0:
         ffc_transpose.py:79-86 on z of shape (B, nz, 1, 1)) is an outer product: out[b, m, y, x] =
         sum_c z[b, c] W[c, m, y, x].  As ONE GEMM with M' = M*k*k "channels" at 1x1 (the output
         (B, M, k, k) has the memory layout of (B, M*k*k, 1, 1)) it fills the GPU with tiles instead
-        of 16 tiny per-phase GEMMs.  -> (segments, weights, M', output shape) or None."""
+        of 16 tiny per-phase GEMMs: on ffc_dense_forward where rt.conv_route says 'dense', as 1x1
+        segments of an implicit-GEMM job otherwise (several segments, or more channels than the dense
+        kernel stages).  -> (segments, weights, M', output shape) or None."""
         if M is None or not segs or not rt.USE_OUTER:
             return None
         k = segs[0].k
         for sg in segs:
             if (sg.kind, sg.IH, sg.IW, sg.s, sg.p, sg.d, sg.op, sg.k) != ("convT", 1, 1, 1, 0, 1, 0, k):
                 return None
-        cache = self._ffc_cache()
+        packs = rt.packs_of(self._ffc_cache())
         segs2, w2 = [], []
-        for sg, (wt, lay, kh, kw, bias) in zip(segs, w):
-            key = ("outer", wt.data_ptr(), rt.weight_key(wt), rt.weight_key(bias))
-            hit = cache.get(key)
-            if hit is None:
-                for old in [kk for kk in cache if kk[0] == "outer" and kk[1] == wt.data_ptr()]:
-                    del cache[old]
-                wr = wt.permute(1, 2, 3, 0).reshape(M * k * k, sg.C, 1, 1).contiguous()   # (C,M,k,k) -> (M k k, C)
-                br = bias.repeat_interleave(k * k).contiguous() if bias is not None else None
-                rt.note_tensors([wr, br])   # the dense launch's packed-weight key is taken from these
-                hit = cache[key] = (wr, br)
+        for sg, wt in zip(segs, w):
+            def build(sg=sg, wt=wt):
+                wr = wt.w.permute(1, 2, 3, 0).reshape(M * k * k, sg.C, 1, 1).contiguous()   # (C,M,k,k) -> (M k k, C)
+                br = wt.bias.repeat_interleave(k * k).contiguous() if wt.bias is not None else None
+                rt.note_tensors([wr, br])   # the launch's packed-weight key is taken from these
+                return wr, br
+            wr, br = packs.get("outer", [wt.w, wt.bias], build)
             segs2.append(_plan.Seg("pw", sg.C, 1, 1))
-            w2.append((hit[0], 0, 1, 1, hit[1]))
+            w2.append(rt.ConvWeight(wr, 0, 1, 1, br))
         return segs2, w2, M * k * k, (M, k, k)
 
     def _launch_dense(self, dense, B, stream):
         """outer-product branches (ConvT on a 1x1 input) as ffc_dense_forward launches; two branches with
         the same input and activation share one launch (their weights concatenated along N, cached)"""
-        cache = self._ffc_cache()
+        packs = rt.packs_of(self._ffc_cache())
         groups = []
         for d in dense:
             for g in groups:
-                if len(g) == 1 and g[0][2].data_ptr() == d[2].data_ptr() and g[0][4] == d[4]:
+                if len(g) == 1 and g[0].x.data_ptr() == d.x.data_ptr() and g[0].act == d.act:
                     g.append(d)
                     break
             else:
                 groups.append([d])
         for g in groups:
-            wts = [d[1] for d in g]
-            key = ("dense",) + tuple((wt[0].data_ptr(), rt.weight_key(wt[0]), rt.weight_key(wt[4])) for wt in wts)
-            hit = cache.get(key)
-            if hit is None:
-                for old in [kk for kk in cache if kk[0] == "dense" and kk[1][0] == key[1][0]]:
-                    del cache[old]
-                Wt = torch.cat([wt[0].reshape(wt[0].shape[0], -1).t() for wt in wts], dim=1).contiguous()
-                has_b = any(wt[4] is not None for wt in wts)
-                bias = torch.cat([wt[4] if wt[4] is not None else torch.zeros(wt[0].shape[0], device=Wt.device)
-                                  for wt in wts]).contiguous() if has_b else None
-                hit = cache[key] = (Wt, bias)
-            Wt, bias = hit
-            x = g[0][2]
+            wts = [d.weight for d in g]
+
+            def build(wts=wts):
+                Wt = torch.cat([wt.w.reshape(wt.w.shape[0], -1).t() for wt in wts], dim=1).contiguous()
+                if all(wt.bias is None for wt in wts):
+                    return Wt, None
+                return Wt, torch.cat([wt.bias if wt.bias is not None else torch.zeros(wt.w.shape[0], device=Wt.device)
+                                      for wt in wts]).contiguous()
+            Wt, bias = packs.get("dense", [t for d in g for t in (d.source.w, d.source.bias)], build)
             K, N = Wt.shape
-            N0 = g[0][5]
-            act = g[0][4]
-            with rt.observe("dense", flops=2.0 * B * K * N):
-                rt.check(rt.lib().ffc_dense_forward(x.data_ptr(), Wt.data_ptr(), rt.ptr(bias), B, K, N, N0,
-                                                    g[0][3].data_ptr(), rt.ptr(g[1][3]) if len(g) > 1 else None,
-                                                    act[0], act[1], stream), "ffc_dense_forward")
-
-    @staticmethod
-    def _smallm_kind(segs, w, addend, bn, M):
-        """<= 4 output channels -> direct VALU kernel: 'convT' for ConvT k4 s2 p1 (the generator's last
-        layer, models/ffc_generator.py:28), 'conv3' for Conv k3 s1 p1 (the fgan128 head conv7,
-        fgan128_complete.py:484), else None"""
-        if not rt.USE_SMALLM or addend is not None or bn is not None or M is None or M > 4 or \
-                not 1 <= len(segs) <= 2:
-            return None
-        if sum(1 for x in w if x[4] is not None) > 1:
-            return None
-        if not all(sg.IH == segs[0].IH and sg.IW == segs[0].IW for sg in segs):
-            return None
-        if all(sg.kind == "convT" and (sg.k, sg.s, sg.p, sg.d, sg.op) == (4, 2, 1, 1, 0) for sg in segs):
-            return "convT"
-        if all(sg.kind == "conv" and sg.k == sg.IH == sg.IW and sg.p == 0 and sg.d == 1 and not sg.pool
-               for sg in segs) and all(x[1] == 0 for x in w):
-            return "full"   # Conv2d onto a 1x1 output (FFCDiscriminator's last layer)
-        if segs[0].IW % 4 == 0 and all(sg.kind == "conv" and (sg.k, sg.s, sg.p, sg.d) == (3, 1, 1, 1) for sg in segs):
-            return "conv3"
-        return None
-
-    def _smallm(self, kind, segs, w, inp, act, M, B, dev, stream, tfs=None):
-        IH, IW = segs[0].IH, segs[0].IW
-        x1 = inp[1][0] if len(inp) > 1 else None
-        w1 = w[1][0] if len(w) > 1 else None
-        bias = next((x[4] for x in w if x[4] is not None), None)
-        C1 = segs[1].C if x1 is not None else 0
-        if kind == "convT":
-            # weights packed [C0 + C1][16 taps][4] by a HIP kernel, cached per (pointer, version)
-            cache = self._ffc_cache()
-            key = ("ctpack", w[0][0].data_ptr(), rt.weight_key(w[0][0]), rt.weight_key(w1))
-            wp = cache.get(key)
-            if wp is None:
-                for old in [kk for kk in cache if kk[0] == "ctpack" and kk[1] == key[1]]:
-                    del cache[old]
-                wp = cache[key] = torch.empty(rt.lib().ffc_convt_smallm_pack_floats(segs[0].C, C1), device=dev,
-                                              dtype=torch.float32)
-                rt.check(rt.lib().ffc_convt_smallm_pack(w[0][0].data_ptr(), segs[0].C, rt.ptr(w1), C1, M,
-                                                        wp.data_ptr(), stream), "ffc_convt_smallm_pack")
-            out = torch.empty((B, M, 2 * IH, 2 * IW), device=dev, dtype=torch.float32)
-            flops = 2.0 * B * M * sum(sg.C for sg in segs) * 4 * (2 * IH) * (2 * IW)
-            with rt.observe("convt_smallm", flops=flops):
-                rt.check(rt.lib().ffc_convt_k4s2_smallm(inp[0][0].data_ptr(), segs[0].C, rt.ptr(x1), C1,
-                                                        wp.data_ptr(), rt.ptr(bias), B, IH, IW, M, out.data_ptr(),
-                                                        act[0], act[1], stream), "ffc_convt_k4s2_smallm")
-            return out
-        if kind == "full":
-            return ag.conv_forward(self._ffc_cache(), ("inf_full",), B, M, tuple(segs), w,
-                                   [x for x, _ in inp], act=act)
-        out = torch.empty((B, M, IH, IW), device=dev, dtype=torch.float32)
-        flops = 2.0 * B * M * sum(sg.C for sg in segs) * 9 * IH * IW
-        if tfs is not None and any(t is not None for t in tfs):
-            st = [t.struct() if t is not None else None for t in tfs] + [None]
-            with rt.observe("conv3_smallm", flops=flops):
-                rt.check(rt.lib().ffc_conv3x3_smallm_tf(inp[0][0].data_ptr(), segs[0].C, w[0][0].data_ptr(),
-                                                        rt.ptr(x1), C1, rt.ptr(w1), rt.ptr(bias), B, IH, IW, M,
-                                                        out.data_ptr(), act[0], act[1],
-                                                        None if st[0] is None else ctypes.byref(st[0]),
-                                                        None if st[1] is None else ctypes.byref(st[1]), stream),
-                         "ffc_conv3x3_smallm_tf")
-            return out
-        with rt.observe("conv3_smallm", flops=flops):
-            rt.check(rt.lib().ffc_conv3x3_smallm(inp[0][0].data_ptr(), segs[0].C, w[0][0].data_ptr(), rt.ptr(x1), C1,
-                                                 rt.ptr(w1), rt.ptr(bias), B, IH, IW, M, out.data_ptr(),
-                                                 act[0], act[1], stream), "ffc_conv3x3_smallm")
-        return out
+            rt.dense_forward(g[0].x, Wt, bias, B, K, N, g[0].N, g[0].out, g[1].out if len(g) > 1 else None,
+                             g[0].act, stream)
 
     def _bn_from_tensor(self, bn, out, stream):
         """batch statistics of a pass-through branch (no GEMM epilogue to collect them)"""

@@ -22,6 +22,7 @@ LAYERS = LAYERS_ALL.get(model, LAYERS_ALL["gen64"])
 
 
 def job_pair(C, IH, M, c):
+    CW = rt.ConvWeight
     g = torch.Generator().manual_seed(C + IH)
     xl = torch.randn(B, C, IH, IH, generator=g).to(dev)
     xg = torch.randn(B, C, IH, IH, generator=g).to(dev)
@@ -32,14 +33,14 @@ def job_pair(C, IH, M, c):
     w2 = torch.randn(M, max(c, 1), 1, 1, generator=g).to(dev) * 0.02
     segT = _plan.Seg("convT", C, IH, IH, 4, 2, 1)
     if c == 0:   # FFCTranspose with ratio_gin 0: out_l = l2l(x_l), out_g = l2g(x_l)
-        return [([segT], [(wl, 1, 4, 4, None)], [xl]), ([segT], [(wlg, 1, 4, 4, None)], [xl])]
-    jobs = [([segT, segT], [(wl, 1, 4, 4, None), (wg, 1, 4, 4, None)], [xl, xg]),
-            ([segT, _plan.Seg("pw", c, 2 * IH, 2 * IH)], [(wlg, 1, 4, 4, None), (w2, 0, 1, 1, None)], [xl, v])]
+        return [([segT], [CW(wl, 1, 4, 4, None)], [xl]), ([segT], [CW(wlg, 1, 4, 4, None)], [xl])]
+    jobs = [([segT, segT], [CW(wl, 1, 4, 4, None), CW(wg, 1, 4, 4, None)], [xl, xg]),
+            ([segT, _plan.Seg("pw", c, 2 * IH, 2 * IH)], [CW(wlg, 1, 4, 4, None), CW(w2, 0, 1, 1, None)], [xl, v])]
     return jobs
 
 
 def time_layer(jobs, reps=20):
-    execs = [rt.ConvExec(B, w[0][0].shape[1] if w[0][1] == 1 else w[0][0].shape[0], segs, w, dev)
+    execs = [rt.ConvExec(B, w[0].w.shape[1] if w[0].layout == 1 else w[0].w.shape[0], segs, w, dev)
              for segs, w, _ in jobs]
     groups = {}
     for e, (segs, w, xs) in zip(execs, jobs):

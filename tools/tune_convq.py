@@ -36,7 +36,7 @@ def main():
                 jobs = P.job_pair(C, IH, M, c)
                 os.environ.pop("FFC_CONVQ_CFG", None)
                 os.environ.pop("FFC_CONVQ_KSPLIT", None)
-                execs = [rt.ConvExec(B, w[0][0].shape[1] if w[0][1] == 1 else w[0][0].shape[0], segs, w, P.dev)
+                execs = [rt.ConvExec(B, w[0].w.shape[1] if w[0].layout == 1 else w[0].w.shape[0], segs, w, P.dev)
                          for segs, w, _ in jobs]
                 base_us = None
                 if any(e.launch_key[0] != "q" for e in execs):   # convp by default: the bar to beat
@@ -64,7 +64,7 @@ def main():
                 pick = min((r for r in res if r[0] <= best[0] * 1.03), key=lambda r: (r[1], r[0]))
                 sigs = []
                 for segs, w, _ in jobs:
-                    Mj = w[0][0].shape[1] if w[0][1] == 1 else w[0][0].shape[0]
+                    Mj = w[0].w.shape[1] if w[0].layout == 1 else w[0].w.shape[0]
                     sigs.append(list(_plan.job_signature(B, Mj, segs)))
                 entries.append({"model": model, "layer": f"C{C}@{IH}x{IH}->M{M}", "jobs": sigs, "cfg": pick[2],
                                 "ksplit": pick[1], "us": round(pick[0], 2),
