@@ -21,6 +21,8 @@ no CPU fallback):
   NoiseInjection (noise_injection.py:25-32)                  ffc::noise_inject  ffc::noise_wgrad
   local Fourier unit's split / cat and repeat + add           ffc::lfu_split     ffc::lfu_split_backward
     (spectral_transform.py:94-108; with set_lfu only)         ffc::lfu_tile_add  ffc::lfu_tile_backward
+  Self_Attn after its stacked projection (attention_layer     ffc::self_attn     ffc::self_attn_bwd
+    .py:30-39; the projection is an ffc::conv_layer)
 
 FFT adjoints (verified in fp64): d/dX of irfftn(ortho) is rfftn(ortho) with the
 mirrored bins doubled; d/dx of rfftn(ortho) is irfftn(ortho) with the mirrored bins halved.
@@ -558,6 +560,121 @@ def linear(lin: nn.Linear, z):
     (y,) = conv_layer(B, [(lin.out_features, 0, 0.0)], [(0, 0, _plan.Seg("pw", K, 1, 1), _LinearAs1x1(lin))],
                       [z.reshape(B, K, 1, 1)])
     return y.reshape(B, lin.out_features)
+
+
+# --------------------------------------------------------------------------- Self_Attn
+def _attn_dims(x, qkv, what):
+    """(B, C, H, W, d) of a Self_Attn call; NotImplementedError naming the shape when the kernels refuse it"""
+    if x.dim() != 4:
+        raise NotImplementedError(f"{what}: x must be (B, C, H, W), got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
+        raise NotImplementedError(f"{what}: unsupported shape {tuple(x.shape)}: the HIP attention kernels take "
+                                  "C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+    d = C // 8
+    if tuple(qkv.shape) != (B, 2 * d + C, H, W):
+        raise RuntimeError(f"{what}: the stacked projection must be {(B, 2 * d + C, H, W)}, got {tuple(qkv.shape)}")
+    return B, C, H, W, d
+
+
+def _attn_rows(qkv, d, N):
+    """device pointers of the q, k, v rows of the stacked projection (B, 2d + C, N)"""
+    base = qkv.data_ptr()
+    return base, base + 4 * d * N, base + 8 * d * N
+
+
+def self_attn_impl(x, qkv, gamma, save):
+    """ffc::self_attn: y = gamma * softmax(q^T k) applied to v + x from the stacked projection qkv (B, 2d + C,
+    H, W) (layers/attention_layer.py:30-39) -> [y, L (B, N) log-sum-exp rows, o (B, C, N) with ``save``, else
+    empty]"""
+    x = rt.require(x, "x")
+    qkv = rt.require(qkv, "qkv")
+    gamma = rt.require(gamma, "gamma")
+    B, C, H, W, d = _attn_dims(x, qkv, "Self_Attn")
+    N = H * W
+    y = torch.empty_like(x)
+    L = torch.empty((B, N), device=x.device, dtype=torch.float32)
+    o = torch.empty((B, C, N) if save else (0,), device=x.device, dtype=torch.float32)
+    q, k, v = _attn_rows(qkv, d, N)
+    with rt.observe("self_attn", flops=2.0 * B * N * N * (d + C)):
+        check(rt.lib().ffc_attn_forward(q, k, v, (2 * d + C) * N, ptr(x), ptr(gamma), ptr(y), ptr(L),
+                                        ptr(o) if save else None, B, C, H, W, _stream(x)), "ffc_attn_forward")
+    return [y, L, o]
+
+
+def self_attn_matrix_impl(qkv, L, C):
+    """ffc::self_attn_matrix: the attention matrix (B, N, N) = exp(S - L) from the stacked projection"""
+    qkv = rt.require(qkv, "qkv")
+    L = rt.require(L, "L")
+    B, _, H, W = qkv.shape
+    d, N = C // 8, H * W
+    P = torch.empty((B, N, N), device=qkv.device, dtype=torch.float32)
+    q, k, _ = _attn_rows(qkv, d, N)
+    with rt.observe("self_attn_matrix", bytes=4.0 * B * N * N):
+        check(rt.lib().ffc_attn_matrix(q, k, (2 * d + C) * N, ptr(L), ptr(P), B, C, H, W, _stream(qkv)),
+              "ffc_attn_matrix")
+    return P
+
+
+def self_attn_bwd_impl(dy, qkv, o, L, gamma):
+    """ffc::self_attn_bwd -> [dqkv (B, 2d + C, H, W), dgamma (1)] (dx of the residual is dy itself)"""
+    dy = rt.require(dy, "dy")
+    qkv = rt.require(qkv, "qkv")
+    B, C, H, W, d = _attn_dims(dy, qkv, "Self_Attn backward")
+    N = H * W
+    if tuple(o.shape) != (B, C, N):
+        raise RuntimeError("Self_Attn backward: the forward ran without save (no attention output kept)")
+    dqkv = torch.empty_like(qkv)
+    dgamma = torch.empty(1, device=dy.device, dtype=torch.float32)
+    ws = torch.empty(rt.lib().ffc_attn_ws_floats(B, C, H, W), device=dy.device, dtype=torch.float32)
+    q, k, v = _attn_rows(qkv, d, N)
+    dq, dk, dv = _attn_rows(dqkv, d, N)
+    with rt.observe("self_attn_bwd", flops=2.0 * B * N * N * (4 * d + 3 * C)):
+        check(rt.lib().ffc_attn_backward(ptr(dy), q, k, v, (2 * d + C) * N, ptr(o), ptr(L), ptr(gamma), dq, dk, dv,
+                                         (2 * d + C) * N, ptr(dgamma), ptr(ws), B, C, H, W, _stream(dy)),
+              "ffc_attn_backward")
+    return [dqkv, dgamma]
+
+
+class _StackedQKV:
+    """query_conv, key_conv and value_conv of a Self_Attn seen by conv_layer as one 1x1 Conv2d with
+    2d + C outputs.  With gradients recording the stack is a fresh cat, so the gradient flows back to the
+    three modules' parameters; otherwise it is kept until a parameter changes (its packed form with it)."""
+
+    def __init__(self, mod, grad):
+        ps = [mod.query_conv.weight, mod.key_conv.weight, mod.value_conv.weight,
+              mod.query_conv.bias, mod.key_conv.bias, mod.value_conv.bias]
+        if grad:
+            self.weight, self.bias = torch.cat(ps[:3]), torch.cat(ps[3:])
+        else:
+            key = tuple((p.data_ptr(), p._version) for p in ps)
+            hit = mod.__dict__.get("_stacked")
+            if hit is None or hit[0] != key:
+                with torch.no_grad():
+                    hit = mod.__dict__["_stacked"] = (key, torch.cat(ps[:3]), torch.cat(ps[3:]))
+            _, self.weight, self.bias = hit
+        self.out_channels = self.weight.shape[0]
+
+
+def self_attn(mod, x):
+    """Self_Attn ``mod`` on x (B, C, H, W) -> (out, attention or None): one stacked projection on the
+    pointwise GEMM (ffc::conv_layer), the fused attention (ffc::self_attn), and with mod.need_attention the
+    attention matrix (ffc::self_attn_matrix, no gradient)"""
+    x = rt.require(x, "x")
+    B, C, H, W = x.shape
+    if C != mod.chanel_in:
+        raise RuntimeError(f"Self_Attn has {mod.chanel_in} channels, tensor has {C}")
+    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
+        raise NotImplementedError(f"Self_Attn: unsupported shape {tuple(x.shape)}: the HIP attention kernels take "
+                                  "C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+    grad = wants_grad(mod, x)
+    M = 2 * (C // 8) + C
+    (qkv,) = conv_layer(B, [(M, 0, 0.0)], [(0, 0, _plan.Seg("pw", C, H, W), _StackedQKV(mod, grad))], [x])
+    y, L, _ = torch.ops.ffc.self_attn(x, qkv, mod.gamma, grad)
+    attention = None
+    if mod.need_attention:
+        attention = torch.ops.ffc.self_attn_matrix(qkv.detach(), L.detach(), C)
+    return y, attention
 
 
 # --------------------------------------------------------------------------- FFTs

@@ -261,6 +261,15 @@ SIGNATURES = [
     ("ffc_sn_ws_bytes", c_size_t, [c_int, c_int]),
     ("ffc_sn_forward", c_int, [ctypes.POINTER(SnJob), c_int, c_int, c_void_p, c_size_t, c_void_p]),
     ("ffc_sn_backward", c_int, [ctypes.POINTER(SnJob), c_int, c_void_p, c_size_t, c_void_p]),
+    ("ffc_attn_supported", c_int, [c_int, c_int, c_int]),
+    ("ffc_attn_ws_floats", c_size_t, [c_int, c_int, c_int, c_int]),
+    ("ffc_attn_forward", c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    ("ffc_attn_matrix", c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                c_void_p]),
+    ("ffc_attn_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int,
+                                  c_int, c_void_p]),
 ]
 
 _lock = threading.Lock()

@@ -594,6 +594,65 @@ def _(dw, w_orig, saved, sigma, dims):
     return [t.new_empty(t.shape) for t in w_orig]
 
 
+# ---------------------------------------------------------------- ffc::self_attn
+# Self_Attn (layers/attention_layer.py:30-39) after its stacked q / k / v projection, on csrc/attn_kernels.hip
+
+
+@torch.library.custom_op("ffc::self_attn", mutates_args=())
+def self_attn(x: Tensor, qkv: Tensor, gamma: Tensor, save: bool) -> List[Tensor]:
+    """-> [y = gamma * attention(qkv) + x, L (B, N), o (B, C, N) for the backward when ``save`` else empty]"""
+    return ag.self_attn_impl(x, qkv, gamma, save)
+
+
+@self_attn.register_fake
+def _(x, qkv, gamma, save):
+    B, C, H, W = x.shape
+    return [torch.empty_like(x), x.new_empty((B, H * W)), x.new_empty((B, C, H * W) if save else (0,))]
+
+
+@torch.library.custom_op("ffc::self_attn_matrix", mutates_args=())
+def self_attn_matrix(qkv: Tensor, L: Tensor, C: int) -> Tensor:
+    """the attention matrix (B, N, N), written only when asked for; carries no gradient"""
+    return ag.self_attn_matrix_impl(qkv, L, C)
+
+
+@self_attn_matrix.register_fake
+def _(qkv, L, C):
+    return qkv.new_empty((L.shape[0], L.shape[1], L.shape[1]))
+
+
+@torch.library.custom_op("ffc::self_attn_bwd", mutates_args=())
+def self_attn_bwd(dy: Tensor, qkv: Tensor, o: Tensor, L: Tensor, gamma: Tensor) -> List[Tensor]:
+    """-> [dqkv, dgamma]; deterministic (no atomics)"""
+    return ag.self_attn_bwd_impl(dy, qkv, o, L, gamma)
+
+
+@self_attn_bwd.register_fake
+def _(dy, qkv, o, L, gamma):
+    return [torch.empty_like(qkv), gamma.new_empty((1,))]
+
+
+def _self_attn_setup(ctx, inputs, output):
+    x, qkv, gamma, save = inputs
+    ctx.saved = bool(save)
+    ctx.gshape = tuple(gamma.shape)
+    if save:
+        ctx.save_for_backward(qkv, output[2], output[1], gamma)
+
+
+def _self_attn_bwd(ctx, grads):
+    dy = grads[0]
+    if dy is None:
+        return None, None, None, None
+    if not ctx.saved:
+        raise RuntimeError("ffc::self_attn ran with save=False; it has no backward")
+    qkv, o, L, gamma = ctx.saved_tensors
+    dqkv, dgamma = torch.ops.ffc.self_attn_bwd(dy, qkv, o, L, gamma)
+    return dy, dqkv, dgamma.view(ctx.gshape), None
+
+
+self_attn.register_autograd(_self_attn_bwd, setup_context=_self_attn_setup)
+
 # =========================================================================== inference ops
 
 

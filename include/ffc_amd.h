@@ -778,6 +778,35 @@ int ffc_sn_forward(const ffc_sn_job* jobs, int n, int training, void* ws, size_t
  * sigma: what the forward of the same call left (u_save / v_save when given). */
 int ffc_sn_backward(const ffc_sn_job* jobs, int n, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ Self_Attn (layers/attention_layer.py:8-40)
+ * With d = C / 8, N = H W, q, k (d rows each) and v (C rows) rows of N floats, sample b of each at
+ * b * bstride floats from its pointer (the stacked projection (B, 2d + C, N): q = base, k = base + d N,
+ * v = base + 2 d N, bstride = (2d + C) N):
+ *   S[i, j] = sum_r q[r, i] k[r, j]     P = softmax over j of S     o[c, i] = sum_j v[c, j] P[i, j]
+ *   y = gamma[0] o + x                  L[b, i] = log sum_j exp S[i, j]
+ * Products are exact fp32 (v_mfma_f32_32x32x2_f32); softmax is online over key tiles of 32, so nothing
+ * N x N is written.  gamma is read on the device.  Supported: C % 8 == 0, 8 <= C <= 64, H, W >= 1,
+ * H W <= 65536, B <= 65535; anything else returns FFC_E_INVALID ("unsupported ...") before any launch.
+ * Pure additions: the ABI version is unchanged. */
+/* 1 when the ffc_attn_* entry points take (C, H, W); needs no device */
+int ffc_attn_supported(int C, int H, int W);
+/* floats of workspace ffc_attn_backward needs (0 when unsupported) */
+size_t ffc_attn_ws_floats(int B, int C, int H, int W);
+/* one launch.  x, y: (B, C, N); L: (B, N); o: (B, C, N) or NULL (the backward's input) */
+int ffc_attn_forward(const float* q, const float* k, const float* v, long long bstride, const float* x,
+                     const float* gamma, float* y, float* L, float* o, int B, int C, int H, int W, void* stream);
+/* the attention matrix on request: P[b, i, j] = exp(S[i, j] - L[b, i]), (B, N, N); one launch */
+int ffc_attn_matrix(const float* q, const float* k, long long bstride, const float* L, float* P, int B, int C,
+                    int H, int W, void* stream);
+/* gradients for dy = dLoss/dy, (B, C, N): dq, dk, dv (sample b at b * gbstride floats) and dgamma[0] =
+ * sum dy o.  (dx = dy, and the projections' own gradients, are the caller's.)  Four launches: D[b, i]
+ * = sum_c dy o with per-workgroup partials of dgamma; their merge in one fixed order; a key-tile-major
+ * kernel that owns dk, dv; a query-tile-major kernel that owns dq.  No atomics: bitwise reproducible.
+ * ws: ffc_attn_ws_floats floats, 16-byte aligned. */
+int ffc_attn_backward(const float* dy, const float* q, const float* k, const float* v, long long bstride,
+                      const float* o, const float* L, const float* gamma, float* dq, float* dk, float* dv,
+                      long long gbstride, float* dgamma, float* ws, int B, int C, int H, int W, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
