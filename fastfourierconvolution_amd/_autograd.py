@@ -577,6 +577,17 @@ def _attn_dims(x, qkv, what):
     return B, C, H, W, d
 
 
+def _attn_L(L, like, B, N, what):
+    """the log-sum-exp rows the kernels index as L[b * N + i]"""
+    if tuple(L.shape) != (B, N) or L.device != like.device:
+        raise RuntimeError(f"{what}: L must be {(B, N)} on {like.device}, got {tuple(L.shape)} on {L.device}")
+
+
+def _attn_gamma(gamma, what):
+    if gamma.numel() != 1:
+        raise RuntimeError(f"{what}: gamma must have one element, got shape {tuple(gamma.shape)}")
+
+
 def _attn_rows(qkv, d, N):
     """device pointers of the q, k, v rows of the stacked projection (B, 2d + C, N)"""
     base = qkv.data_ptr()
@@ -591,6 +602,7 @@ def self_attn_impl(x, qkv, gamma, save):
     qkv = rt.require(qkv, "qkv")
     gamma = rt.require(gamma, "gamma")
     B, C, H, W, d = _attn_dims(x, qkv, "Self_Attn")
+    _attn_gamma(gamma, "Self_Attn")
     N = H * W
     y = torch.empty_like(x)
     L = torch.empty((B, N), device=x.device, dtype=torch.float32)
@@ -606,8 +618,18 @@ def self_attn_matrix_impl(qkv, L, C):
     """ffc::self_attn_matrix: the attention matrix (B, N, N) = exp(S - L) from the stacked projection"""
     qkv = rt.require(qkv, "qkv")
     L = rt.require(L, "L")
-    B, _, H, W = qkv.shape
+    what = "Self_Attn matrix"
+    if qkv.dim() != 4:
+        raise RuntimeError(f"{what}: qkv must be 4-D (B, 2d + C, H, W), got {tuple(qkv.shape)}")
+    B, M, H, W = qkv.shape
+    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
+        raise NotImplementedError(f"{what}: unsupported shape (B, C, H, W) = {(B, C, H, W)}: the HIP attention "
+                                  "kernels take C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
     d, N = C // 8, H * W
+    if M != 2 * d + C:
+        raise RuntimeError(f"{what}: the stacked projection of C = {C} must be {(B, 2 * d + C, H, W)}, got "
+                           f"{tuple(qkv.shape)}")
+    _attn_L(L, qkv, B, N, what)
     P = torch.empty((B, N, N), device=qkv.device, dtype=torch.float32)
     q, k, _ = _attn_rows(qkv, d, N)
     with rt.observe("self_attn_matrix", bytes=4.0 * B * N * N):
@@ -620,10 +642,16 @@ def self_attn_bwd_impl(dy, qkv, o, L, gamma):
     """ffc::self_attn_bwd -> [dqkv (B, 2d + C, H, W), dgamma (1)] (dx of the residual is dy itself)"""
     dy = rt.require(dy, "dy")
     qkv = rt.require(qkv, "qkv")
+    o = rt.require(o, "o")
+    L = rt.require(L, "L")
+    gamma = rt.require(gamma, "gamma")
     B, C, H, W, d = _attn_dims(dy, qkv, "Self_Attn backward")
     N = H * W
     if tuple(o.shape) != (B, C, N):
-        raise RuntimeError("Self_Attn backward: the forward ran without save (no attention output kept)")
+        raise RuntimeError("Self_Attn backward: the forward ran without save (no attention output kept): o must be "
+                           f"{(B, C, N)}, got {tuple(o.shape)}")
+    _attn_L(L, dy, B, N, "Self_Attn backward")
+    _attn_gamma(gamma, "Self_Attn backward")
     dqkv = torch.empty_like(qkv)
     dgamma = torch.empty(1, device=dy.device, dtype=torch.float32)
     ws = torch.empty(rt.lib().ffc_attn_ws_floats(B, C, H, W), device=dy.device, dtype=torch.float32)
