@@ -10,8 +10,6 @@
 
 namespace ffc {
 
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) { return __shfl_xor(v, m, 64); }
-
 // BLOCK threads (whole waves).  A wave reads 4 partial rows x 16 consecutive channels per load
 // (four 256-byte segments); lane = 16 rg + oc.  The waves of a 16-channel block split its rows
 // ((wave-in-block, rg) interleaved), merge rg with a fixed xor tree, and the wave partials meet
@@ -174,10 +172,6 @@ __device__ __forceinline__ double permlane_sum_f64(double v) {
 // (each v += partner(v) with an involutive partner): every lane of a group holds the bit-identical sum
 template <int L>
 __device__ __forceinline__ double group_sum_f64(double v) {
-#ifdef FFC_FOLD_SHFL
-    for (int m = 1; m < L; m <<= 1) v += shfl_xor_f64(v, m);
-    return v;
-#endif
     if constexpr (L >= 2) v += dpp_full_f64<0xB1>(v);     // quad_perm [1,0,3,2]: lane ^ 1
     if constexpr (L >= 4) v += dpp_full_f64<0x4E>(v);     // quad_perm [2,3,0,1]: lane ^ 2
     if constexpr (L >= 8) v += dpp_full_f64<0x141>(v);    // row_half_mirror: the other quad of the 8
@@ -206,13 +200,7 @@ __device__ inline void bn_fold_channels(const ffc_bn_fold& f, int o, bool leader
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int r = r0 + L * u;
-#ifdef FFC_FOLD_PLAIN_LOADS   // DESIGN 10c probe: plain global loads instead of the buffer descriptor
-            const float4 pv = r < f.nrows ? reinterpret_cast<const float4*>(f.slab)[(size_t)r * f.C + o]
-                                          : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            e[u] = floatx4{pv.x, pv.y, pv.z, pv.w};
-#else
             e[u] = buf_ld4(rs, r < f.nrows ? (unsigned)((r * f.C + o) * 16) : OOB);
-#endif
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
@@ -225,10 +213,6 @@ __device__ inline void bn_fold_channels(const ffc_bn_fold& f, int o, bool leader
     n = group_sum_f64<L>(n);
     s = group_sum_f64<L>(s);
     q = group_sum_f64<L>(q);
-#ifdef FFC_FOLD_FIN1   // DESIGN 10c probe: the fp64 finalize in lane 0 of each group only (others: 0)
-    scale = shift = 0.0f;
-    if (gl == 0)
-#endif
     bn_fold_finalize(f, o, n, s, q, leader && gl == 0, 0, scale, shift);   // momentum >= 0: nbt unused
 }
 

@@ -454,7 +454,6 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_c2r_kernel(C2rArgs a) {
         Z[r * ZS + WP] = make_float2(ahx - bhy, ahy + bhx);
     }
     __syncthreads();
-#ifndef FFC_C2R_SKIP_COL   // timing probes only (tools/build_variant.sh): results are wrong without it
     {
         constexpr int N1c = Split<H>::N1, LPR = FU2_THREADS / N1c;
         const int jj = tid % N1c;
@@ -463,7 +462,6 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_c2r_kernel(C2rArgs a) {
             if (l < W / 2) line_fft<H, true>(Z + (l == 0 ? WP : l), ZS, jj, twc);
         }
     }
-#endif
     __syncthreads();
 
     // 3. rows two at a time: z[k] = A_ext[k] + i B_ext[k] (Hermitian extension of each half
@@ -498,17 +496,9 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_c2r_kernel(C2rArgs a) {
                     re[m] = A.x - B.y;
                     im[m] = A.y + B.x;
                 }
-#ifndef FFC_C2R_SKIP_ROW
                 stage_a<W, true>(re, im, twr);
                 float ore[Q][N1], oim[Q][N1];
                 stage_b<W, true>(ra, 1, re, im, jj, ore, oim);
-#else
-                float ore[Q][N1], oim[Q][N1];
-#pragma unroll
-                for (int q = 0; q < Q; ++q)
-#pragma unroll
-                    for (int k1 = 0; k1 < N1; ++k1) { ore[q][k1] = re[q * N1 + k1]; oim[q][k1] = im[q * N1 + k1]; }
-#endif
                 float* fa = reinterpret_cast<float*>(ra);   // 4*ZS >= 2W floats: row 2g then row 2g+1
 #pragma unroll
                 for (int q = 0; q < Q; ++q)
@@ -618,19 +608,13 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 
 // The wave's A operand: fp32 fragments in registers (compile-time C, C*MT <= 64), fp16 fragments in
 // registers (F16), or read from the LDS copy Wm per k-step.
-#ifdef FFC_MIX_F32   // A/B measurement builds: the register-resident fp32 mix on the f32-input MFMA
-constexpr bool MIX_SPLIT = false;
-#else
-constexpr bool MIX_SPLIT = true;
-#endif
-
 template <int MT, int CC, bool F16, bool NOAREG = false, bool SPLITOK = true>
 struct MixA {
     static constexpr bool AREG = !NOAREG && !F16 && CC > 0 && CC * MT <= 64;
     // fp32 mix with register-resident weights: fp32-accurate split-bf16 products (ffc_internal.h
     // split3), the weights split once per workgroup; element j of lane half hh in k-block q is
     // k = 2 (8q + j) + hh, i.e. channel 8q + j, Re (hh = 0) or Im (hh = 1)
-    static constexpr bool SPLIT = AREG && MIX_SPLIT && SPLITOK && CC % 8 == 0;
+    static constexpr bool SPLIT = AREG && SPLITOK && CC % 8 == 0;
     float areg[AREG ? CC : 1][MT];
     Split3 as3[SPLIT ? CC / 8 : 1][SPLIT ? MT : 1];
     half8 a16[F16 ? MT : 1][F16 ? CC / 8 : 1];
@@ -919,37 +903,6 @@ struct R2cMixLds {
     static constexpr int FLOATS = WM + SCR + TL + R + 2 * CC;
 };
 
-#ifdef FFC_R2CMIX_DUMP   // DESIGN 10c probe build: Tl after the row FFTs (slot 0) and at the end (slot 1)
-__device__ float g_r2cmix_dump[512 * 2 * 4608];
-#endif
-#if defined(FFC_R2CMIX_CANARY) || defined(FFC_R2CMIX_FCANARY)
-__device__ int g_r2cmix_canary_hits;
-#endif
-#if defined(FFC_R2CMIX_DBG) || defined(FFC_R2CMIX_DBGEND)
-// DESIGN 10c probe build: per workgroup, per channel: bn1 scale, shift, sum R, sum |T| after the row
-// FFTs, sum |T| after the column FFTs (thread ch sums its channel in a fixed order)
-__device__ float g_r2cmix_dbg[4096 * 5 * 32];
-#define R2CMIX_DBG(slot, expr_of_ch)                                                        \
-    do {                                                                                    \
-        __syncthreads();                                                                    \
-        if (tid < C) {                                                                      \
-            const int ch = tid;                                                             \
-            g_r2cmix_dbg[((size_t)blockIdx.x * 5 + (slot)) * 32 + ch] = (expr_of_ch);       \
-        }                                                                                   \
-        __syncthreads();                                                                    \
-    } while (0)
-template <int N>
-__device__ float dbg_sum(const float* p, int stride) {
-    float s = 0.0f;
-    for (int i = 0; i < N; ++i) s += fabsf(p[i * stride]);
-    return s;
-}
-#endif
-#ifndef FFC_R2CMIX_DBG
-#undef R2CMIX_DBG
-#define R2CMIX_DBG(slot, e) do { } while (0)
-#endif
-
 template <int MT, int CC, int HT>
 __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra) {
     using LY = R2cMixLds<HT, CC>;
@@ -957,12 +910,7 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra
     static_assert((CC & (CC - 1)) == 0 && CC <= FU2_THREADS / 4 && (C * HT * HT) % (4 * FU2_THREADS) == 0,
                   "whole float4 rounds of the sample");
     const MixArgs& a = ra.m;
-#ifdef FFC_R2CMIX_FRONTPAD   // DESIGN 10c probe: unused LDS IN FRONT of the layout
-    extern __shared__ __attribute__((aligned(16))) float smem_front[];
-    float* const smem = smem_front + FFC_R2CMIX_FRONTPAD / 4;
-#else
     extern __shared__ __attribute__((aligned(16))) float smem[];
-#endif
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int hh = lane >> 5, col = lane & 31;
     const int b = blockIdx.x % a.B;
@@ -978,85 +926,21 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra
     // 1. the sample's t planes (registers) and the mix weight (LDS-DMA), all in flight
     constexpr int NV = C * HT * HT / 4 / FU2_THREADS;
     const float4* src = reinterpret_cast<const float4*>(ra.t + (size_t)b * C * HT * HT);
-#if defined(FFC_R2CMIX_ZERO_LDS) || defined(FFC_R2CMIX_ZERO_SCR)   // DESIGN 10c probes
-#ifdef FFC_R2CMIX_ZERO_LDS
-    for (int i = tid; i < LY::FLOATS; i += FU2_THREADS) smem[i] = 0.0f;
-#else
-    for (int i = tid; i < LY::SCR; i += FU2_THREADS) scr[i] = 0.0f;
-#endif
-    __syncthreads();
-#endif
-#ifdef FFC_R2CMIX_CANARY   // DESIGN 10c probe: a canary in the LDS padding behind the layout (FFC_R2CMIX_PAD)
-    for (int i = tid; i < FFC_R2CMIX_PAD / 4; i += FU2_THREADS) smem[LY::FLOATS + i] = __int_as_float(0x7fc0dead);
-    __syncthreads();
-#endif
-#ifdef FFC_R2CMIX_FCANARY  // DESIGN 10c probe: a canary in the LDS padding in front of the layout (FFC_R2CMIX_FRONTPAD)
-    for (int i = tid; i < FFC_R2CMIX_FRONTPAD / 4; i += FU2_THREADS) smem_front[i] = __int_as_float(0x7fc0beef);
-    __syncthreads();
-#endif
-#ifdef FFC_R2CMIX_V192    // DESIGN 10c probe: 192 VGPRs reserved -> at most two workgroups per CU, layout unpadded
-    asm volatile("" ::: "v191");
-#endif
     float4 v[NV];
-#ifndef FFC_R2CMIX_LATE_T
 #pragma unroll
     for (int j = 0; j < NV; ++j) v[j] = src[j * FU2_THREADS + tid];
-#endif
-#ifdef FFC_R2CMIX_NODMA   // DESIGN 10c probe: the mix weight through registers instead of LDS-DMA
-    for (int i = tid; i < (C2 * a.Mpad) >> 2; i += FU2_THREADS)
-        reinterpret_cast<float4*>(Wm)[i] = reinterpret_cast<const float4*>(a.wmixT)[i];
-#else
     ffc::dma_copy16(a.wmixT, Wm, (C2 * a.Mpad) >> 2, tid, FU2_THREADS);
-#endif
     // 2. bn1 (under the loads' latency): the whole-slab fold, scratch in the (not yet used) tile-stats
-    //    area.  The per-channel fold (ffc::bn_fold_channels, as in the staged r2c) was measured
-    //    non-deterministic here -- T of two channels wrong in a few workgroups per launch (r05i,
-    //    tools/experiments/r2cmix_*.py) -- and bn_fold_block is not.
+    //    area.  The per-channel fold of the staged r2c (ffc::bn_fold_channels) gave non-deterministic
+    //    results in this kernel and bn_fold_block does not.
     if (ra.has_fold) {
-#ifdef FFC_R2CMIX_CHFOLD
-#ifdef FFC_R2CMIX_DMA_WAIT
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-#ifdef FFC_R2CMIX_PREBAR
-        __syncthreads();
-#endif
-#ifdef FFC_R2CMIX_WAVE0   // DESIGN 10c probe: wave 0 alone folds (64 / C lanes per channel)
-        constexpr int L = 64 / C;
-        if (tid < 64) {
-#else
-        constexpr int L = FU2_THREADS / C;
-        {
-#endif
-        float s_, h_;
-        const int o = tid / L;
-#ifdef FFC_R2CMIX_NOLEAD
-        constexpr bool lead = false;
-#else
-        const bool lead = blockIdx.x == 0;
-#endif
-        ffc::bn_fold_channels<L>(ra.fold, o, lead, s_, h_);
-        if ((tid & (L - 1)) == 0) {
-            fss[o] = s_;
-            fss[C + o] = h_;
-        }
-        if (lead && tid == 0 && ra.fold.update_running) *ra.fold.num_batches_tracked += 1;
-        }
-#ifdef FFC_R2CMIX_NOP
-        asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_nop 7" ::: "memory");
-#endif
-#else
         ffc::bn_fold_block<FU2_THREADS>(ra.fold, fss, fss + C, blockIdx.x == 0, reinterpret_cast<double*>(scr));
-#endif
     } else if (tid < C) {
         fss[tid] = ra.in_scale ? ra.in_scale[tid] : 1.0f;
         fss[C + tid] = ra.in_scale ? ra.in_shift[tid] : 0.0f;
     }
     ffc::dma_wait();
     __syncthreads();
-#ifdef FFC_R2CMIX_LATE_T
-#pragma unroll
-    for (int j = 0; j < NV; ++j) v[j] = src[j * FU2_THREADS + tid];
-#endif
     // 3. s0 = relu(t * scale + shift) -> R
 #pragma unroll
     for (int j = 0; j < NV; ++j) {
@@ -1071,12 +955,6 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra
         reinterpret_cast<float4*>(R)[i] = q;
     }
     __syncthreads();
-    R2CMIX_DBG(0, fss[ch]);
-    R2CMIX_DBG(1, fss[C + ch]);
-    R2CMIX_DBG(2, (dbg_sum<HT * HT>(R + ch * HT * HT, 1)));
-#if FFC_R2CMIX_XB == 3   // DESIGN 10c probes: one extra barrier after step 3 / 4 / 5
-    __syncthreads();
-#endif
     // 4. row FFTs (row r = channel * HT + y), bins 0..HT/2 -> Tl[r * WPt + k]
     for (int r = tid; r < C * HT; r += FU2_THREADS) {
         float re[HT], im[HT];
@@ -1095,16 +973,6 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra
         for (int k = 0; k < WPt; ++k) Tl[r * WPt + k] = make_float2(re[k], im[k]);
     }
     __syncthreads();
-    R2CMIX_DBG(3, (dbg_sum<2 * PT>(reinterpret_cast<const float*>(Tl + ch * PT), 1)));
-#ifdef FFC_R2CMIX_DUMP
-    if (blockIdx.x < 512 && LY::TL <= 4608)
-        for (int i = tid; i < LY::TL; i += FU2_THREADS)
-            g_r2cmix_dump[((size_t)blockIdx.x * 2) * 4608 + i] = reinterpret_cast<const float*>(Tl)[i];
-    __syncthreads();   // every wave's dump reads precede the column pass's writes
-#endif
-#if FFC_R2CMIX_XB == 4
-    __syncthreads();
-#endif
     // 5. column FFTs (line l = channel * WPt + k)
     for (int l = tid; l < C * WPt; l += FU2_THREADS) {
         const int ch = l / WPt, k = l - ch * WPt;
@@ -1121,10 +989,6 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra
         for (int y = 0; y < HT; ++y) cp[y * WPt] = make_float2(re[y], im[y]);
     }
     __syncthreads();
-    R2CMIX_DBG(4, (dbg_sum<2 * PT>(reinterpret_cast<const float*>(Tl + ch * PT), 1)));
-#if FFC_R2CMIX_XB == 5
-    __syncthreads();
-#endif
 
     // 6. mix pass 0 on T in LDS: raw Y spill + BN partials (as fu2d_mix_kernel<MT, 0, CC>)
     MixA<MT, CC, false> A;
@@ -1182,55 +1046,7 @@ __global__ __launch_bounds__(FU2_THREADS) void fu2d_r2c_mix_kernel(R2cMixArgs ra
             }
         }
         reinterpret_cast<float4*>(a.slab)[(size_t)blockIdx.x * C2 + o] = make_float4(nn, mean, m2, 0.0f);
-#ifdef FFC_R2CMIX_DBGEND   // DESIGN 10c probe: the workgroup's stage checksums, taken at its very end
-        g_r2cmix_dbg[((size_t)blockIdx.x * 5 + 3) * 32 + o] = m2;
-#endif
     }
-#ifdef FFC_R2CMIX_DUMP
-    __syncthreads();
-    if (blockIdx.x < 512 && LY::TL <= 4608)
-        for (int i = tid; i < LY::TL; i += FU2_THREADS)
-            g_r2cmix_dump[((size_t)blockIdx.x * 2 + 1) * 4608 + i] = reinterpret_cast<const float*>(Tl)[i];
-#endif
-#ifdef FFC_R2CMIX_CANARY
-    __syncthreads();
-    {
-        int first = -1, cnt = 0;
-        for (int i = tid; i < FFC_R2CMIX_PAD / 4; i += FU2_THREADS)
-            if (__float_as_int(smem[LY::FLOATS + i]) != 0x7fc0dead) {
-                if (first < 0) first = i;
-                ++cnt;
-            }
-        if (cnt && atomicAdd(&g_r2cmix_canary_hits, 1) < 40)
-            printf("r2cmix canary: blk %d tid %d first pad float %d (layout float %d) count %d\n", (int)blockIdx.x,
-                   tid, first, LY::FLOATS + first, cnt);
-    }
-#endif
-#ifdef FFC_R2CMIX_FCANARY
-    __syncthreads();
-    {
-        int last = -1, cnt = 0;
-        for (int i = tid; i < FFC_R2CMIX_FRONTPAD / 4; i += FU2_THREADS)
-            if (__float_as_int(smem_front[i]) != 0x7fc0beef) {
-                last = i;
-                ++cnt;
-            }
-        if (cnt && atomicAdd(&g_r2cmix_canary_hits, 1) < 40)
-            printf("r2cmix front canary: blk %d tid %d last pad float %d (layout offset %d) count %d\n",
-                   (int)blockIdx.x, tid, last, last - FFC_R2CMIX_FRONTPAD / 4, cnt);
-    }
-#endif
-#ifdef FFC_R2CMIX_DBGEND
-    __syncthreads();
-    if (tid < C) {
-        const int ch = tid;
-        g_r2cmix_dbg[((size_t)blockIdx.x * 5 + 0) * 32 + ch] = fss[ch];
-        g_r2cmix_dbg[((size_t)blockIdx.x * 5 + 1) * 32 + ch] = fss[C + ch];
-        g_r2cmix_dbg[((size_t)blockIdx.x * 5 + 2) * 32 + ch] = dbg_sum<HT * HT>(R + ch * HT * HT, 1);
-        g_r2cmix_dbg[((size_t)blockIdx.x * 5 + 4) * 32 + ch] =
-            dbg_sum<2 * PT>(reinterpret_cast<const float*>(Tl + ch * PT), 1);
-    }
-#endif
 }
 
 // ---------------------------------------------------------------- pass 1 + inverse column FFT
@@ -1633,17 +1449,6 @@ R2cMixKernel pick_r2c_mix(int C, int h, size_t& lds) {
 }
 }  // namespace
 
-#ifdef FFC_R2CMIX_DUMP
-extern "C" int ffc_debug_r2cmix_dump(void* dst, size_t bytes) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_r2cmix_dump), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif
-#if defined(FFC_R2CMIX_DBG) || defined(FFC_R2CMIX_DBGEND)
-extern "C" int ffc_debug_r2cmix_read(void* dst, size_t bytes) {
-    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_r2cmix_dbg), bytes, 0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
-}
-#endif
-
 extern "C" int ffc_fu2d_r2c_mix_supported(int C, int H, int W, int up) {
     size_t lds = 0;
     return ffc_fu2d_supported(C, H, W, up) && pick_r2c_mix(C, H / up, lds) != nullptr && lds <= 160 * 1024;
@@ -1661,15 +1466,6 @@ extern "C" int ffc_fu2d_r2c_mix(const float* t, int B, int C, int H, int W, int 
                   "scale_out / shift_out");
     size_t lds = 0;
     R2cMixKernel k = pick_r2c_mix(C, H / up, lds);
-#ifdef FFC_R2CMIX_ONEWG   // DESIGN 10c probe: a dynamic LDS request that admits one workgroup per CU
-    lds = 90 * 1024;
-#endif
-#ifdef FFC_R2CMIX_PAD     // DESIGN 10c probe: unused LDS behind the layout, still two workgroups per CU
-    lds += FFC_R2CMIX_PAD;
-#endif
-#ifdef FFC_R2CMIX_FRONTPAD
-    lds += FFC_R2CMIX_FRONTPAD;
-#endif
     int rc = ffc::raise_dynamic_lds(k, lds, "ffc_fu2d_r2c_mix");
     if (rc) return rc;
     R2cMixArgs ra;
