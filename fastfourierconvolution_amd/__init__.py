@@ -9,8 +9,16 @@ plus the restated callers FFCModel / FFCGenerator / FFCDiscriminator / FGenerato
 class-conditional FCondGenerator / FCondDiscriminator (fgan128_cond_complete.py) and the 8*mg family
 FGenerator32 / Discriminator32 / FDiscriminator32 (fgan_complete.py; 32x32 at mg = 4, 48x48 at mg = 6) with its
 conditional-batch-norm variant ConditionalBatchNorm2d / FCondGenerator32 / FCondGeneratorSTL / CondDiscriminator32 /
-FCondDiscriminator32 (layers/cond/cond_bn.py, fgan_cond_complete.py; set_cond_bn).  All compute runs in
-the gfx950 HIP library libffc_amd.so (include/ffc_amd.h); there is no CPU fallback.
+FCondDiscriminator32 (layers/cond/cond_bn.py, fgan_cond_complete.py; set_cond_bn), and the plain
+transposed-conv baselines the FFC generators are compared against: Generator32 (``Generator`` of
+fgan_complete.py), Generator64 (``Generator`` of fgan64_complete.py) and DCGenerator32 (``Generator`` of
+sngan_complete.py):
+
+    G = Generator32(z_size=128, mg=4).cuda().eval()      # Generator64 / DCGenerator32 alike
+    with torch.no_grad():
+        img_u8 = G(torch.randn(64, 128, device="cuda"))  # (64, 3, 32, 32) uint8; G.forward_float(z): the float image
+
+All compute runs in the gfx950 HIP library libffc_amd.so (include/ffc_amd.h); there is no CPU fallback.
 """
 from . import ops  # noqa: F401  (registers the torch.ops.ffc.* custom ops)
 from .config import Config
@@ -19,13 +27,14 @@ from .ffc import (FFC, FFC_BN_ACT, SNFFC, ConditionalBatchNorm2d, FFCTranspose, 
                   spectral_norm_ffc)
 from .attention_layer import Self_Attn
 from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
-from .models import (CondDiscriminator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
+from .models import (CondDiscriminator32, DCGenerator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
                      FCondGenerator, FCondGenerator32, FCondGeneratorSTL, FDiscriminator32, FFCDiscriminator,
-                     FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32)
+                     FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32, Generator32, Generator64)
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
            "SNFFCTranspose", "spectral_norm_ffc", "set_sn_hip", "set_mix_precision", "set_lfu", "Resizer",
            "Print", "debug_print", "NoiseInjection", "FFCModel", "FFCGenerator", "FFCDiscriminator", "FGenerator",
            "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "FGenerator32",
            "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",
-           "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32", "Self_Attn"]
+           "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32", "Self_Attn",
+           "Generator32", "Generator64", "DCGenerator32"]

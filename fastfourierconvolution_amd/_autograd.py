@@ -248,6 +248,18 @@ def conv_layer_impl(xs, ws, bs, spec):
     return outs + pres
 
 
+def _is_convt3_job(outs_s, edges, e, x, ws):
+    """edge e is the only segment of its output and that job ran on conv_route's 'convT3' kernel: its data
+    gradient then runs on ffc_convt3x3_smallm_dgrad (same switch, same caps as the forward)"""
+    j = edges[e][0]
+    if sum(1 for ed in edges if ed[0] == j) != 1:
+        return False
+    bias = x.new_empty(0) if edges[e][9] >= 0 else None
+    w = rt.ConvWeight(ws[e], edges[e][8], edges[e][3], edges[e][3], bias)
+    return rt.conv_route((_edge_seg(edges[e], x),), [w], outs_s[j][0], False, False, rt.TRAIN_ROUTES,
+                         training=True) == "convT3"
+
+
 def conv_layer_backward_impl(xs, ws, ts, gouts, needs, spec):
     """ffc::conv_layer_backward: ts[j] = output j (its pre-activation for GELU); needs: per x, w, b.
     -> [dx per x, dW per w, db per b] (empty tensors where not needed)"""
@@ -269,6 +281,11 @@ def conv_layer_backward_impl(xs, ws, ts, gouts, needs, spec):
             grads[i] = torch.zeros_like(x)
             continue
         C = x.shape[1]
+        if len(es) == 1 and _is_convt3_job(outs_s, edges, es[0][0], x, ws):
+            # the small-M 3x3 transposed head: its adjoint (a Conv2d from <= 4 to C channels) on the direct kernel
+            e, ed = es[0]
+            grads[i] = rt.convt3_dgrad(gs[ed[0]], ws[e].contiguous(), tuple(x.shape), _stream(x))
+            continue
         adj = []
         for e, ed in es:
             g = gs[ed[0]]

@@ -216,6 +216,10 @@ SIGNATURES = [
     ("ffc_convt_smallm_pack", c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     ("ffc_convt_k4s2_smallm", c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int,
                                       c_int, c_int, c_void_p, c_int, c_float, c_void_p]),
+    ("ffc_convt3x3_smallm", c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int,
+                                    c_float, c_void_p]),
+    ("ffc_convt3x3_smallm_dgrad", c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                          c_void_p]),
     ("ffc_act_bwd", c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_int, c_float, c_void_p]),
     ("ffc_reduce_splits", c_int, [c_int, c_int, c_int]),
     ("ffc_channel_moments", c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),

@@ -765,7 +765,7 @@ PRESPLIT_A = _env("FFC_CONVP_PRESPLIT", "0", lambda s: s == "1")   # A/B knob: A
 USE_CONVQ = _env("FFC_CONVQ", "auto", _not0)
 CONVQ_FORCE = _env("FFC_CONVQ", "auto", lambda s: s in ("1", "force"))
 USE_OUTER = True   # inference: ConvT on a 1x1 input as one outer-product GEMM (conv_route, _FFCExec._outer_rewrite)
-USE_SMALLM = True  # direct VALU kernels for <= 4 output channels (conv_route 'convT' / 'full' / 'conv3')
+USE_SMALLM = True  # direct VALU kernels for <= 4 output channels (conv_route 'convT' / 'full' / 'conv3' / 'convT3')
 FORCE_FU2D = False  # large-plane FU stages even where the fused per-sample FU applies (tests)
 # SpectralTransform prologue: "auto" = the fused per-sample kernel where the sample fits in LDS
 # (st_prologue.hip), else SE gate + gated 1x1 GEMM (st_pw.hip); "pw" forces the latter (A/B runs)
@@ -823,12 +823,13 @@ class RouteCaps:
     CONVT_SMALLM_CMAX = 256   # CT_CMAX in csrc/convt_smallm.hip (ffc_convt_k4s2_smallm: both segments' channels)
     CONV3_SMALLM_CMAX = 256   # CMAX3 in csrc/convt_smallm.hip (ffc_conv3x3_smallm: both segments' channels)
     DENSE_KMAX = 256          # DN_KMAX in csrc/dense.hip (ffc_dense_forward: the A tile's K staged in LDS)
+    CONVT3_SMALLM_CMAX = 256  # CT3_CMAX in csrc/convt3_smallm.hip (ffc_convt3x3_smallm and its data gradient)
 
 
-INFER_ROUTES = frozenset(("convT", "full", "conv3", "dense"))
+INFER_ROUTES = frozenset(("convT", "full", "conv3", "dense", "convT3"))
 # _autograd.conv_forward has never sent a job to the 3x3 kernel (its 3x3 jobs run on the implicit-GEMM
 # kernels); that answer is kept
-TRAIN_ROUTES = frozenset(("convT", "full", "dense"))
+TRAIN_ROUTES = frozenset(("convT", "full", "dense", "convT3"))
 
 
 def conv_route(segs, weights, M, has_addend, has_bn, accept, training=False):
@@ -838,6 +839,8 @@ def conv_route(segs, weights, M, has_addend, has_bn, accept, training=False):
       'convT'  <= 4 output channels, ConvTranspose2d k4 s2 p1 (the generator's last layer): ffc_convt_k4s2_smallm
       'full'   <= 4 output channels, Conv2d onto a 1x1 output (FFCDiscriminator's last layer): ffc_conv_full_smallm
       'conv3'  <= 4 output channels, Conv2d k3 s1 p1 on rows of 4n pixels (the fgan128 head): ffc_conv3x3_smallm
+      'convT3' <= 4 output channels, one ConvTranspose2d k3 s1 p1 segment on rows of any width (the head of the
+               baseline generators): ffc_convt3x3_smallm; its data gradient is ffc_convt3x3_smallm_dgrad
       'dense'  ConvTranspose2d(k, s=1, p=0) on a 1x1 input (the generators' first layer), a plain GEMM
                out (B, M k k) = x (B, C) . W (C, M k k): ffc_dense_forward
     No direct kernel adds an addend, collects BN partials, pools or gates its input, or takes two biases.
@@ -860,6 +863,10 @@ def conv_route(segs, weights, M, has_addend, has_bn, accept, training=False):
         elif all(sg.kind == "conv" and (sg.k, sg.s, sg.p, sg.d) == (3, 1, 1, 1) for sg in segs):
             if one_plane and segs[0].IW % 4 == 0 and C <= RouteCaps.CONV3_SMALLM_CMAX:
                 route = "conv3"
+        elif len(segs) == 1 and segs[0].kind == "convT" and \
+                (segs[0].k, segs[0].s, segs[0].p, segs[0].d, segs[0].op) == (3, 1, 1, 1, 0):
+            if layouts == {1} and C <= RouteCaps.CONVT3_SMALLM_CMAX:
+                route = "convT3"
     sg = segs[0]
     if route is None and len(segs) == 1 and sg.kind == "convT" and layouts == {1} and C <= RouteCaps.DENSE_KMAX and \
             (sg.IH, sg.IW, sg.s, sg.p, sg.d, sg.op) == (1, 1, 1, 0, 1, 0):
@@ -872,7 +879,7 @@ def conv_route(segs, weights, M, has_addend, has_bn, accept, training=False):
 
 
 def smallm_forward(route, segs, weights, xs, M, B, act, stream, packs=None, pack_slot=None, tfs=None):
-    """launch the direct kernel of a 'convT' / 'full' / 'conv3' job (conv_route) -> out.
+    """launch the direct kernel of a 'convT' / 'full' / 'conv3' / 'convT3' job (conv_route) -> out.
     packs, pack_slot: the PackCache (and its slot, see there) for the convT kernel's packed weights;
     tfs: per input, the PendingAct whose
     BN + activation (+ noise) the 3x3 kernel applies as it stages that input (or None)"""
@@ -904,6 +911,11 @@ def smallm_forward(route, segs, weights, xs, M, B, act, stream, packs=None, pack
                                           a, ap, stream), "ffc_convt_k4s2_smallm")
         return out
     out = torch.empty((B, M, IH, IW), device=dev, dtype=torch.float32)
+    if route == "convT3":   # the raw (C, M, 3, 3) weight as it stands: nothing to pack
+        with observe("convt3_smallm", flops=2.0 * B * M * C0 * 9 * IH * IW):
+            check(L.ffc_convt3x3_smallm(ptr(xs[0]), C0, ptr(w0), ptr(bias), B, IH, IW, M, ptr(out), a, ap, stream),
+                  "ffc_convt3x3_smallm")
+        return out
     head = (ptr(xs[0]), C0, ptr(w0), ptr(x1), C1, ptr(w1), ptr(bias), B, IH, IW, M, ptr(out), a, ap)
     with observe("conv3_smallm", flops=2.0 * B * M * (C0 + C1) * 9 * IH * IW):
         if tfs is not None and any(t is not None for t in tfs):
@@ -914,6 +926,17 @@ def smallm_forward(route, segs, weights, xs, M, B, act, stream, packs=None, pack
         else:
             check(L.ffc_conv3x3_smallm(*head, stream), "ffc_conv3x3_smallm")
     return out
+
+
+def convt3_dgrad(dpre, w, x_shape, stream):
+    """data gradient of a 'convT3' job: dx (B, C, H, W) from dpre (B, M, H, W) and the raw weight (C, M, 3, 3)"""
+    B, C, H, W = x_shape
+    M = dpre.shape[1]
+    dx = torch.empty((B, C, H, W), device=dpre.device, dtype=torch.float32)
+    with observe("convt3_dgrad", flops=2.0 * B * M * C * 9 * H * W):
+        check(lib().ffc_convt3x3_smallm_dgrad(ptr(dpre), ptr(w), B, C, H, W, M, ptr(dx), stream),
+              "ffc_convt3x3_smallm_dgrad")
+    return dx
 
 
 def dense_forward(x, Wt, bias, B, K, N, N0, out0, out1, act, stream):

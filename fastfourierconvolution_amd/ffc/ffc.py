@@ -305,7 +305,7 @@ class _FFCExec:
                     outs[br.name] = addend.clone()
                     post.append(_Post(br.name, outs[br.name], br.act, br.bn, None, 0))
                 continue
-            if route in ("convT", "full", "conv3"):
+            if route in ("convT", "full", "conv3", "convT3"):
                 outs[br.name] = rt.smallm_forward(route, br.segs, br.weights, br.inputs, br.M, B, br.act, stream,
                                                   rt.packs_of(cache))
                 continue

@@ -12,6 +12,11 @@ restated as FGenerator32, Discriminator32 and FDiscriminator32: ``FGenerator`` a
 name the fgan128 classes here.  Its class-conditional variant, fgan_cond_complete.py (conditional batch
 norm on bn_l / bn_g of every FFC_BN_ACT), is FCondGenerator32, FCondGeneratorSTL, CondDiscriminator32
 and FCondDiscriminator32.
+
+The reference names three more classes ``Generator``: the plain transposed-conv baselines its drivers switch
+to by moving a comment.  They are Generator32 (fgan_complete.py:34-79, the 8*mg family), Generator64
+(fgan64_complete.py:34-82, 16*mg planes) and DCGenerator32 (sngan_complete.py:82-113, the DCGAN stack on a 1x1
+z).
 """
 import os
 
@@ -292,6 +297,129 @@ class Discriminator32(Discriminator):
     def __init__(self, sn: bool = True, mg: int = 4):
         super().__init__(sn=sn, mg=mg)
         del self.last_act
+
+
+def _run_stack(seq, x):
+    """a Sequential of ConvTranspose2d / BatchNorm2d + ReLU / Tanh (the baseline generators' ``model`` and
+    ``last``) on the HIP ops: every ConvTranspose2d one ffc::conv_layer job with its bias (a following Tanh in
+    its epilogue), every BatchNorm2d + ReLU pair one ffc::bn_act (+ the running-statistics update in train
+    mode)"""
+    mods = list(seq)
+    i = 0
+    while i < len(mods):
+        m = mods[i]
+        nxt = mods[i + 1] if i + 1 < len(mods) else None
+        if isinstance(m, nn.ConvTranspose2d):
+            act = (0, 0.0)
+            if isinstance(nxt, nn.Tanh):
+                act = rt.act_code(nxt)
+                i += 1
+            (x,) = ag.conv_layer(x.shape[0], [(m.out_channels,) + tuple(act)], [(0, 0, rt.conv_seg(m, x), m)], [x])
+        elif isinstance(m, nn.BatchNorm2d) and isinstance(nxt, nn.ReLU):
+            x = ag.bn_act(m, x, rt.act_code(nxt))
+            i += 1
+        else:
+            raise NotImplementedError(f"{type(m).__name__} in a baseline generator stack")
+        i += 1
+    return x
+
+
+def _ct_bn_relu(chans):
+    """ConvTranspose2d(k4, s2, p1) + BatchNorm2d + ReLU per consecutive channel pair"""
+    mods = []
+    for cin, cout in zip(chans, chans[1:]):
+        mods += [nn.ConvTranspose2d(cin, cout, 4, stride=2, padding=(1, 1)), nn.BatchNorm2d(cout), nn.ReLU()]
+    return mods
+
+
+class Generator32(FFCModel):
+    """fgan_complete.py:34-79 (``Generator`` there): the plain transposed-conv baseline the FFC generator of the
+    8*mg family (FGenerator32) is compared against.  noise_to_feature = Linear(z, mg*mg*512) -> (512, mg, mg) ->
+    ``model``: three ConvTranspose2d(k4, s2, p1) with bias, each + BatchNorm2d + ReLU, 512 -> 256 -> 128 -> 64 ->
+    ``attn`` = Self_Attn(64, 'relu') on the 8mg x 8mg plane -> ``last``: ConvTranspose2d(64, 3, 3, s1, p1) +
+    Tanh.  Constructor, attribute names and state_dict keys are the reference's.
+
+    Everything runs on the HIP ops (no torch compute): the Linear on ffc::linear / ag.linear, each transposed
+    conv as one ffc::conv_layer job, BatchNorm2d + ReLU on ffc::bn_act (running statistics,
+    num_batches_tracked and momentum as nn.BatchNorm2d; under distributed.enable_sync_bn the batch moments are
+    all-reduced like every other BatchNorm of the package), the head on the direct small-M kernel
+    (conv_route 'convT3') with Tanh in its epilogue.
+
+    The reference computes the (B, N, N) attention matrix and drops it (``fake, out = self.attn(fake)``);
+    here ``self.attn.need_attention`` is set False in the constructor, so the matrix is never allocated (the
+    class default of Self_Attn stays True).
+
+    Eval mode returns the uint8 image of :72-77: the clamp to the batch's own min / max is the identity, so it
+    is ffc::quantize_u8 of the float image.  ``forward_float(z)`` stops at the float image."""
+
+    TRUNK = (512, 256, 128, 64)
+
+    def __init__(self, z_size, mg: int = 4):
+        super().__init__()
+        self.z_size = z_size
+        self.mg = mg
+        self.ngf = 64
+        self.noise_to_feature = nn.Linear(z_size, (self.mg * self.mg) * self.ngf * 8)
+        self.model = nn.Sequential(*_ct_bn_relu(self.TRUNK))
+        from .attention_layer import Self_Attn
+        self.attn = Self_Attn(64, "relu")
+        self.attn.need_attention = False
+        self.last = nn.Sequential(nn.ConvTranspose2d(64, 3, 3, stride=1, padding=(1, 1)), nn.Tanh())
+
+    def forward_float(self, z):
+        lin = self.noise_to_feature
+        z = rt.require(z, "z")
+        if z.dim() != 2 or z.shape[1] != lin.in_features:
+            raise RuntimeError(f"{type(self).__name__}: z must be (B, {lin.in_features}), got {tuple(z.shape)}")
+        if ag.wants_grad(lin, z):
+            fake = ag.linear(lin, z)
+        else:
+            fake = torch.ops.ffc.linear(z, lin.weight, lin.bias)
+        fake = _run_stack(self.model, fake.reshape(z.shape[0], -1, self.mg, self.mg))
+        fake, _ = self.attn(fake)
+        return _run_stack(self.last, fake)
+
+    def forward(self, z):
+        fake = self.forward_float(z)
+        if self.training:
+            return fake
+        return torch.ops.ffc.quantize_u8(fake)
+
+
+class Generator64(Generator32):
+    """fgan64_complete.py:34-82 (``Generator`` there): Generator32 with a fourth ConvTranspose2d(64, 64, k4, s2,
+    p1) + BatchNorm2d + ReLU, so the attention and the head run on the 16mg x 16mg plane (64 x 64 at mg = 4)."""
+
+    TRUNK = (512, 256, 128, 64, 64)
+
+
+class DCGenerator32(nn.Module):
+    """sngan_complete.py:82-113 (``Generator`` there): the DCGAN baseline.  One ``model`` Sequential:
+    ConvTranspose2d(z, 512, 4, s1) on the 1x1 z, three ConvTranspose2d(k4, s2, p1), each of the four +
+    BatchNorm2d + ReLU, then ConvTranspose2d(64, 3, 3, s1, p1) + Tanh: a 32 x 32 image.  No Linear, no attention;
+    ``mg`` is accepted and unused, as in the reference.  The layers run as Generator32's do.  Eval mode returns
+    uint8(255 * (clamp(x, -1, 1) * 0.5 + 0.5)) (:109-111): on a Tanh output that clamp is the identity, so it is
+    ffc::quantize_u8 too."""
+
+    def __init__(self, z_size, mg):
+        super().__init__()
+        self.z_size = z_size
+        self.print_layer = Print(debug=True)
+        self.model = nn.Sequential(nn.ConvTranspose2d(z_size, 512, 4, stride=1), nn.BatchNorm2d(512), nn.ReLU(),
+                                   *_ct_bn_relu((512, 256, 128, 64)),
+                                   nn.ConvTranspose2d(64, 3, 3, stride=1, padding=(1, 1)), nn.Tanh())
+
+    def forward_float(self, z):
+        z = rt.require(z, "z")
+        if z.numel() % self.z_size:
+            raise RuntimeError(f"DCGenerator32: z must hold (B, {self.z_size}) values, got {tuple(z.shape)}")
+        return _run_stack(self.model, z.reshape(-1, self.z_size, 1, 1))
+
+    def forward(self, z):
+        fake = self.forward_float(z)
+        if self.training:
+            return fake
+        return torch.ops.ffc.quantize_u8(fake)
 
 
 class FDiscriminator32(FFCModel):

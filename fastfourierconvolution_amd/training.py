@@ -33,7 +33,7 @@ def generator_step(G, D, optim_G, optim_D, z, noises=None, labels=None):
     optim_D.zero_grad()
     optim_G.zero_grad()
     if labels is None:
-        fake = G(z, noises)
+        fake = G(z) if noises is None else G(z, noises)   # the baseline generators take z alone
         loss_G = hinge_loss_gen(D(fake))
     else:
         fake = G(z, labels, noises)
@@ -53,7 +53,7 @@ def discriminator_step(G, D, optim_G, optim_D, z, real, noises=None, labels=None
     optim_D.zero_grad()
     optim_G.zero_grad()
     if labels is None:
-        fake = G(z, noises)
+        fake = G(z) if noises is None else G(z, noises)   # the baseline generators take z alone
         output_dg = D(fake)
         output_dreal = D(real)
     else:

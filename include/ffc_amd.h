@@ -360,6 +360,19 @@ int ffc_conv3x3_smallm(const float* x0, int C0, const float* w0, const float* x1
                        const float* w1, const float* bias, int B, int H, int W, int M, float* out,
                        int act, float act_param, void* stream);
 
+/* Direct ConvTranspose2d(k=3, s=1, p=1) for M <= 4 output channels (the head of the baseline generators,
+ * fgan_complete.py:58-61, fgan64_complete.py:61-64, sngan_complete.py:103-104) and its data gradient:
+ *   out (B, M, H, W) = act(conv_t(x; w) + bias),   dx (B, C, H, W) = conv(dpre; w)  (dpre: the gradient of the
+ *   pre-activation, (B, M, H, W)).
+ * w: the raw ConvTranspose2d weight (C, M, 3, 3), read as it stands; bias (M) may be NULL; C <= 256.  Any H
+ * and W: rows are moved as aligned float4 groups when W % 4 == 0 and x / out (dpre / dx) are 16-byte aligned,
+ * by bounds-checked scalar accesses otherwise.  Deterministic (no atomics).  M > 4, C > 256, a NULL x, w,
+ * out, dpre or dx and B, C, H or W <= 0 return FFC_E_INVALID before any launch. */
+int ffc_convt3x3_smallm(const float* x, int C, const float* w, const float* bias, int B, int H, int W, int M,
+                        float* out, int act, float act_param, void* stream);
+int ffc_convt3x3_smallm_dgrad(const float* dpre, const float* w, int B, int C, int H, int W, int M, float* dx,
+                              void* stream);
+
 /* Deferred input transform of one conv input segment: the producing FFC_BN_ACT's BatchNorm2d +
  * activation and the NoiseInjection that follows it (ffc_bn_act.py:80-83 then
  * noise_injection.py:25-32; fgan128_complete.py:509-513), applied while the consumer stages its
