@@ -4,7 +4,7 @@
 
 exports FourierUnitSN, SELayer, SpectralTransform, FFC, FFCTranspose, FFC_BN_ACT, SNFFC, SNFFCTranspose
 (layers/snffc), Resizer,
-Print, debug_print, NoiseInjection, GaussianNoise, Self_Attn (the names layers/__init__.py:2-18 exports for this path)
+Print, debug_print, NoiseInjection, GaussianNoise, Self_Attn, aw_method (the names layers/__init__.py:2-18 exports for this path)
 plus the restated callers FFCModel / FFCGenerator / FFCDiscriminator / FGenerator and Discriminator (fgan128), the
 class-conditional FCondGenerator / FCondDiscriminator (fgan128_cond_complete.py) and the 8*mg family
 FGenerator32 / Discriminator32 / FDiscriminator32 (fgan_complete.py; 32x32 at mg = 4, 48x48 at mg = 6) with its
@@ -26,6 +26,7 @@ from .ffc import (FFC, FFC_BN_ACT, SNFFC, ConditionalBatchNorm2d, FFCTranspose, 
                   SNFFCTranspose, SpectralTransform, set_cond_bn, set_lfu, set_mix_precision, set_sn_hip,
                   spectral_norm_ffc)
 from .attention_layer import Self_Attn
+from .aw_loss import aw_method
 from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_print
 from .models import (CondDiscriminator32, DCGenerator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
                      FCondGenerator, FCondGenerator32, FCondGeneratorSTL, FDiscriminator32, FFCDiscriminator,
@@ -37,4 +38,4 @@ __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose
            "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "FGenerator32",
            "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",
            "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32", "Self_Attn",
-           "Generator32", "Generator64", "DCGenerator32"]
+           "Generator32", "Generator64", "DCGenerator32", "aw_method"]

@@ -1264,3 +1264,62 @@ def sn_weights(mods, hooks):
     ws = SpectralNormWeight.apply(layers, modes.pop(), *[getattr(m, h.name + "_orig") for m, h in zip(mods, hooks)])
     for m, h, w in zip(mods, hooks, ws):
         setattr(m, h.name, w)
+
+
+# --------------------------------------------------------------------------- adaptive-weight loss
+AW_JOBS_PER_LAUNCH = 0   # gradient pairs per launch of ffc_aw_*: 1..16; 0: the library's 16 (tests vary the split)
+AW_STATS = 8             # [rr, ff, rf, rs, fs, w_r, w_f, case]
+
+
+def _aw_lists(g_real, g_fake, out=None):
+    """the pointer / numel arrays of ffc_aw_* for two gradient lists (and the outputs)"""
+    import ctypes
+    n = len(g_real)
+    if not n or len(g_fake) != n or (out is not None and len(out) != n):
+        raise RuntimeError("aw: g_real, g_fake (and out) must be lists of the same non-zero length")
+    lists = [g_real, g_fake] + ([out] if out is not None else [])
+    for i in range(n):
+        for ts, what in zip(lists, ("g_real", "g_fake", "out")):
+            t = ts[i]
+            rt.require(t, f"aw: {what}[{i}]")
+            if not t.is_contiguous():
+                raise FFCError(f"aw: {what}[{i}] must be contiguous")
+            if t.numel() != g_real[i].numel() or t.device != g_real[0].device:
+                raise RuntimeError(f"aw: {what}[{i}] does not match g_real[{i}] (numel, device)")
+    arrays = [(ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]) for ts in lists]
+    numel = (ctypes.c_longlong * n)(*[t.numel() for t in g_real])
+    return arrays, numel, n
+
+
+def aw_weights_impl(g_real, g_fake, real_validity, fake_validity, alpha1, alpha2, delta, epsilon, normalized):
+    """ffc::aw_weights -> stats (8,) fp64 = [rr, ff, rf, rs, fs, w_r, w_f, case]: the dots of the two
+    gradient lists per 16384-element chunk, then one workgroup for the weights of aw_loss.py:49-96
+    (ceil(n / 16) + 1 launches); nothing leaves the device"""
+    (pr, pf), numel, n = _aw_lists(g_real, g_fake)
+    rv, fv = rt.require(real_validity, "aw: real_validity"), rt.require(fake_validity, "aw: fake_validity")
+    if not (alpha1 < alpha2):
+        raise RuntimeError("aw_weights: alpha1 < alpha2")
+    if not rv.numel() or not fv.numel():
+        raise RuntimeError("aw_weights: empty logits")
+    dev = g_real[0].device
+    L = rt.lib()
+    nws = L.ffc_aw_ws_doubles(numel, n)
+    ws = torch.empty(nws, device=dev, dtype=torch.float64)
+    stats = torch.empty(AW_STATS, device=dev, dtype=torch.float64)
+    with rt.observe("aw_weights", bytes=sum(8.0 * t.numel() for t in g_real)):
+        check(L.ffc_aw_weights(pr, pf, numel, n, ptr(rv), rv.numel(), ptr(fv), fv.numel(), float(alpha1),
+                               float(alpha2), float(delta), float(epsilon), 1 if normalized else 0,
+                               AW_JOBS_PER_LAUNCH, ptr(ws), nws, ptr(stats), _stream(g_real[0])), "ffc_aw_weights")
+    return stats
+
+
+def aw_combine_impl(g_real, g_fake, stats, out):
+    """ffc::aw_combine: out[i] <- (float)w_r * g_real[i] + (float)w_f * g_fake[i], the weights read from
+    ``stats`` on the device (ceil(n / 16) launches)"""
+    (pr, pf, po), numel, n = _aw_lists(g_real, g_fake, out)
+    if stats.dtype != torch.float64 or stats.numel() != AW_STATS or not stats.is_contiguous() or \
+            stats.device != g_real[0].device:
+        raise RuntimeError("aw_combine: stats must be the (8,) fp64 tensor of aw_weights")
+    with rt.observe("aw_combine", bytes=sum(12.0 * t.numel() for t in g_real)):
+        check(rt.lib().ffc_aw_combine(pr, pf, po, numel, n, ptr(stats), AW_JOBS_PER_LAUNCH, _stream(g_real[0])),
+              "ffc_aw_combine")

@@ -274,6 +274,13 @@ SIGNATURES = [
     ("ffc_attn_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int,
                                   c_int, c_void_p]),
+    ("ffc_aw_chunk", c_int, []),
+    ("ffc_aw_ws_doubles", c_size_t, [ctypes.POINTER(c_longlong), c_int]),
+    ("ffc_aw_weights", c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_int,
+                               c_void_p, c_longlong, c_void_p, c_longlong, c_double, c_double, c_double, c_double,
+                               c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("ffc_aw_combine", c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                               ctypes.POINTER(c_longlong), c_int, c_void_p, c_int, c_void_p]),
 ]
 
 _lock = threading.Lock()

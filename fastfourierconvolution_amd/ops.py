@@ -594,6 +594,35 @@ def _(dw, w_orig, saved, sigma, dims):
     return [t.new_empty(t.shape) for t in w_orig]
 
 
+# ---------------------------------------------------------------- ffc::aw_weights / ffc::aw_combine
+# aw_method.aw_loss (layers/aw_loss.py:13-107) after its two gradient passes, on csrc/aw_kernels.hip; the
+# module is aw_loss.aw_method
+
+
+@torch.library.custom_op("ffc::aw_weights", mutates_args=())
+def aw_weights(g_real: List[Tensor], g_fake: List[Tensor], real_validity: Tensor, fake_validity: Tensor,
+               alpha1: float, alpha2: float, delta: float, epsilon: float, normalized: bool) -> Tensor:
+    """-> stats (8,) fp64 on the device: [rr, ff, rf, rs, fs, w_r, w_f, case]"""
+    return ag.aw_weights_impl(g_real, g_fake, real_validity, fake_validity, alpha1, alpha2, delta, epsilon,
+                              normalized)
+
+
+@aw_weights.register_fake
+def _(g_real, g_fake, real_validity, fake_validity, alpha1, alpha2, delta, epsilon, normalized):
+    return real_validity.new_empty((ag.AW_STATS,), dtype=torch.float64)
+
+
+@torch.library.custom_op("ffc::aw_combine", mutates_args=("out",))
+def aw_combine(g_real: List[Tensor], g_fake: List[Tensor], stats: Tensor, out: List[Tensor]) -> None:
+    """out[i] <- w_r * g_real[i] + w_f * g_fake[i], the weights read from ``stats`` on the device"""
+    ag.aw_combine_impl(g_real, g_fake, stats, out)
+
+
+@aw_combine.register_fake
+def _(g_real, g_fake, stats, out):
+    return None
+
+
 # ---------------------------------------------------------------- ffc::self_attn
 # Self_Attn (layers/attention_layer.py:30-39) after its stacked q / k / v projection, on csrc/attn_kernels.hip
 

@@ -16,6 +16,16 @@ def hinge_loss_dis(fake, real):
     return tF.relu(1.0 - real).mean() + tF.relu(1.0 + fake).mean()
 
 
+def hinge_loss_real(real):
+    """fgan128_complete.py:574-576: the real half of hinge_loss_dis"""
+    return tF.relu(1.0 - real).mean()
+
+
+def hinge_loss_fake(fake):
+    """fgan128_complete.py:578-579: the fake half of hinge_loss_dis"""
+    return tF.relu(1.0 + fake).mean()
+
+
 def hinge_loss_gen(fake):
     """fgan128_complete.py:581-585"""
     assert fake.dim() == 2 and fake.shape[1] == 1, f"{fake.shape}"
@@ -62,6 +72,29 @@ def discriminator_step(G, D, optim_G, optim_D, z, real, noises=None, labels=None
         output_dreal = D(real, labels)
     loss_D = hinge_loss_dis(output_dg, output_dreal)
     loss_D.backward()
+    optim_D.step()
+    return loss_D
+
+
+def aw_discriminator_step(G, D, optim_G, optim_D, z, real, aw, noises=None, labels=None):
+    """discriminator_step with the adaptive-weight loss (layers/aw_loss.py) in place of hinge_loss_dis:
+    the same two critic calls, then ``aw.aw_loss`` (an aw_loss.aw_method) over the two hinge halves, which
+    takes both gradients through the one retained graph and leaves w_r * g_real + w_f * g_fake in
+    D's ``.grad``s, then optim_D.step().  Under set_sn_hip SpectralNormWeight.backward runs once per
+    gradient pass on the tensors it saved; the two passes share nothing they write."""
+    G.requires_grad_(False)
+    D.requires_grad_(True)
+    optim_G.zero_grad()
+    if labels is None:
+        fake = G(z) if noises is None else G(z, noises)
+        output_dg = D(fake)
+        output_dreal = D(real)
+    else:
+        fake = G(z, labels, noises)
+        output_dg = D(fake, labels)
+        output_dreal = D(real, labels)
+    loss_D = aw.aw_loss(hinge_loss_real(output_dreal), hinge_loss_fake(output_dg), optim_D, D, output_dreal,
+                        output_dg)
     optim_D.step()
     return loss_D
 

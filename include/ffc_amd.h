@@ -820,6 +820,38 @@ int ffc_attn_backward(const float* dy, const float* q, const float* k, const flo
                       const float* o, const float* L, const float* gamma, float* dq, float* dk, float* dv,
                       long long gbstride, float* dgamma, float* ws, int B, int C, int H, int W, void* stream);
 
+/* ------------------------------------------------------------------ adaptive-weight critic loss
+ * aw_method.aw_loss (layers/aw_loss.py:13-107) after its two backward passes: from the critic's two
+ * gradient lists g_real[i], g_fake[i] (n pairs of contiguous fp32 tensors of numel[i] elements; pairs
+ * with numel[i] == 0 are skipped) and the two logit tensors,
+ *   rr = sum g_r^2 + 1e-4    ff = sum g_f^2 + 1e-4    rf = sum g_r g_f      (over the whole list)
+ *   rs = mean sigmoid(real_validity)    fs = mean sigmoid(fake_validity)     (fp64 from the fp32 logits)
+ *   1 / 2:  rs < alpha1 or rs < fs - delta:   w_r = N_r + eps,  w_f = (rf <= 0 ? -rf / (ff n_r) : 0) + eps
+ *   3 / 4:  rs > alpha2 and rs > fs - delta:  w_f = N_f + eps,  w_r = (rf <= 0 ? -rf / (rr n_f) : 0) + eps
+ *   5:      otherwise:                        w_r = N_r + eps,  w_f = N_f + eps
+ * with normalized (Algorithm 1): n_r = sqrt(rr), n_f = sqrt(ff), N_r = 1 / n_r, N_f = 1 / n_f; otherwise
+ * (Algorithm 2): n_r = n_f = N_r = N_f = 1.  The even case of each pair is rf > 0.
+ *   stats (8 doubles, device) = [rr, ff, rf, rs, fs, w_r, w_f, case]
+ *   out[i] = (float)w_r * g_real[i] + (float)w_f * g_fake[i]
+ * ffc_aw_weights: a workgroup per ffc_aw_chunk() = 16384 elements of one tensor writes three fp64
+ * partials (products of fp32 values are exact in fp64); one workgroup merges them by their global
+ * (tensor, chunk) index in a fixed tree and writes stats.  ffc_aw_combine: one elementwise pass.
+ * At most 16 pairs ride in one launch's arguments: ceil(n' / 16) + 1 and ceil(n' / 16) launches for n'
+ * non-empty pairs (jobs_per_launch in 1..16 lowers the 16; anything else: 16).  No atomics; the results
+ * are bitwise reproducible and do not depend on jobs_per_launch, the device's CU count or the alignment
+ * (16-byte accesses when a pair's tensors are 16-byte aligned, 4-byte otherwise, same summation tree).
+ * The weights stay on the device: nothing synchronises, both calls can be captured into a graph.
+ * ws: ffc_aw_ws_doubles(numel, n) doubles; out[i] must overlap neither input.  Pure additions: the ABI
+ * version is unchanged. */
+int ffc_aw_chunk(void);
+size_t ffc_aw_ws_doubles(const long long* numel, int n);
+int ffc_aw_weights(const float* const* g_real, const float* const* g_fake, const long long* numel, int n,
+                   const float* real_validity, long long n_real, const float* fake_validity, long long n_fake,
+                   double alpha1, double alpha2, double delta, double epsilon, int normalized, int jobs_per_launch,
+                   double* ws, size_t ws_doubles, double* stats, void* stream);
+int ffc_aw_combine(const float* const* g_real, const float* const* g_fake, float* const* out, const long long* numel,
+                   int n, const double* stats, int jobs_per_launch, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
