@@ -191,6 +191,14 @@ __global__ __launch_bounds__(SN_THREADS) void sn_matvec_kernel(SnTable t, int tr
                 acc = fmaf(x.z, pv.z, acc);
                 acc = fmaf(x.w, pv.w, acc);
             }
+        } else if (j.R % 4 == 0) {   // w_orig off 16-byte alignment: the float4 form's order from 4-byte loads
+            for (int q = lane * 4; q < kn; q += 256) {
+                const float* x = row + sn_col(j, kc0 + q);
+                acc = fmaf(x[0], p[q], acc);
+                acc = fmaf(x[1], p[q + 1], acc);
+                acc = fmaf(x[2], p[q + 2], acc);
+                acc = fmaf(x[3], p[q + 3], acc);
+            }
         } else {
             for (int q = lane; q < kn; q += 64) acc = fmaf(row[sn_col(j, kc0 + q)], p[q], acc);
         }
@@ -288,6 +296,15 @@ __global__ __launch_bounds__(SN_THREADS) void sn_dot_kernel(SnTable t) {
             const float4 y = reinterpret_cast<const float4*>(b)[i];
             s += ((double)x.x * (double)y.x + (double)x.y * (double)y.y) +
                  ((double)x.z * (double)y.z + (double)x.w * (double)y.w);
+        }
+        done = n4 << 2;
+    } else {        // the same tree from 4-byte loads: pdot does not depend on the alignment
+        const int n4 = n >> 2;
+        for (int i = tid; i < n4; i += SN_THREADS) {
+            const float* x = a + 4 * i;
+            const float* y = b + 4 * i;
+            s += ((double)x[0] * (double)y[0] + (double)x[1] * (double)y[1]) +
+                 ((double)x[2] * (double)y[2] + (double)x[3] * (double)y[3]);
         }
         done = n4 << 2;
     }

@@ -767,7 +767,8 @@ int ffc_cbn_bwd_apply(const float* x, const float* dy, const int64_t* labels, co
  * results do not depend on what else is in the table.  sigma stays on the device.
  * Workspace: ffc_sn_ws_bytes(M, K) bytes per layer at byte offset ws_off (a multiple of 16) of ws;
  * 0 for M, K <= 0 or M * K >= 2^31.  16-byte accesses when R % 4 == 0 (rows) / the tensors are 16-byte
- * aligned (elementwise passes), 4-byte otherwise.  Pure additions: the ABI version is unchanged. */
+ * aligned (elementwise passes), 4-byte otherwise, in the same summation order: the results do not
+ * depend on the alignment.  Pure additions: the ABI version is unchanged. */
 typedef struct ffc_sn_job {
     const float* w_orig;   /* M * K floats */
     float* u;              /* (M): read; written in training mode */
