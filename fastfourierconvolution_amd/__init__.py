@@ -12,7 +12,8 @@ conditional-batch-norm variant ConditionalBatchNorm2d / FCondGenerator32 / FCond
 FCondDiscriminator32 (layers/cond/cond_bn.py, fgan_cond_complete.py; set_cond_bn), and the plain
 transposed-conv baselines the FFC generators are compared against: Generator32 (``Generator`` of
 fgan_complete.py), Generator64 (``Generator`` of fgan64_complete.py) and DCGenerator32 (``Generator`` of
-sngan_complete.py):
+sngan_complete.py), and the ResNet SNGAN-128 baseline GBlock / DBlock / DBlockOptimized / SNGANGenerator128 /
+SNGANDiscriminator128 (fgan128_complete.py:75-438; resnet.py):
 
     G = Generator32(z_size=128, mg=4).cuda().eval()      # Generator64 / DCGenerator32 alike
     with torch.no_grad():
@@ -31,6 +32,7 @@ from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_pr
 from .models import (CondDiscriminator32, DCGenerator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
                      FCondGenerator, FCondGenerator32, FCondGeneratorSTL, FDiscriminator32, FFCDiscriminator,
                      FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32, Generator32, Generator64)
+from .resnet import DBlock, DBlockOptimized, GBlock, SNGANDiscriminator128, SNGANGenerator128
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
            "SNFFCTranspose", "spectral_norm_ffc", "set_sn_hip", "set_mix_precision", "set_lfu", "Resizer",
@@ -38,4 +40,5 @@ __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose
            "Discriminator", "FGanDiscriminator", "FCondGenerator", "FCondDiscriminator", "FGenerator32",
            "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",
            "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32", "Self_Attn",
-           "Generator32", "Generator64", "DCGenerator32", "aw_method"]
+           "Generator32", "Generator64", "DCGenerator32", "aw_method", "GBlock", "DBlock", "DBlockOptimized",
+           "SNGANGenerator128", "SNGANDiscriminator128"]

@@ -195,11 +195,21 @@ def parse_conv_spec(spec: str):
     return [tuple(o) for o in d["outs"]], [tuple(e) for e in d["edges"]]
 
 
-def conv_spec(outs, edges) -> str:
-    """outs: [(M, act, param)]; edges: [(j, i, Seg, layout, bias index or -1)] -> spec string"""
-    return json.dumps({"outs": [[int(M), int(a), float(p)] for M, a, p in outs],
-                       "edges": [[j, i, sg.kind, sg.k, sg.s, sg.p, sg.d, sg.op, lay, b] for j, i, sg, lay, b in edges]},
-                      separators=(",", ":"))
+@functools.lru_cache(maxsize=4096)
+def parse_conv_adds(spec: str):
+    """{output j: input i}: xs[i] (the output's shape, no edge reads it) is added to output j before its
+    activation -- a residual block's identity shortcut (the kernels' ``addend``)"""
+    return {int(j): int(i) for j, i in json.loads(spec).get("adds", ())}
+
+
+def conv_spec(outs, edges, adds=None) -> str:
+    """outs: [(M, act, param)]; edges: [(j, i, Seg, layout, bias index or -1)]; adds: [(j, i)] (parse_conv_adds)
+    -> spec string"""
+    d = {"outs": [[int(M), int(a), float(p)] for M, a, p in outs],
+         "edges": [[j, i, sg.kind, sg.k, sg.s, sg.p, sg.d, sg.op, lay, b] for j, i, sg, lay, b in edges]}
+    if adds:
+        d["adds"] = [[int(j), int(i)] for j, i in adds]
+    return json.dumps(d, separators=(",", ":"))
 
 
 def _edge_seg(e, x) -> _plan.Seg:
@@ -223,6 +233,7 @@ def conv_layer_out_shape(e, x, M):
 def conv_layer_impl(xs, ws, bs, spec):
     """ffc::conv_layer: -> outputs, then the pre-activation of every GELU output (the backward's input)"""
     outs_s, edges = parse_conv_spec(spec)
+    adds = parse_conv_adds(spec)
     rt.note_tensors(list(ws) + list(bs))
     xs = [rt.require(x, "conv_layer input") for x in xs]
     ws = [rt.require(w, "conv_layer weight") for w in ws]
@@ -236,9 +247,16 @@ def conv_layer_impl(xs, ws, bs, spec):
         wts = [rt.ConvWeight(ws[e], edges[e][8], edges[e][3], edges[e][3],
                              bs[edges[e][9]] if edges[e][9] >= 0 else None) for e in es]
         fused = act if act != 5 else 0
+        addend = None
+        if j in adds:
+            addend = xs[adds[j]]
+            if any(ed[1] == adds[j] for ed in edges):
+                raise NotImplementedError("conv_layer: an input that is an addend may feed no edge of the same op")
+            if tuple(addend.shape) != tuple(conv_layer_out_shape(edges[es[0]], xs[edges[es[0]][1]], M)):
+                raise RuntimeError(f"conv_layer: addend {tuple(addend.shape)} is not output {j}'s shape")
         with _CL_POOL.hold() as cache:
             y = conv_forward(cache, ("fwd", spec, j, B, sgs), B, M, sgs, wts, [xs[edges[e][1]] for e in es],
-                             act=(fused, param))
+                             act=(fused, param), addend=addend)
         if act == 5:
             pres.append(y)
             y = _act_out(y, act, param, _stream(y))
@@ -272,8 +290,13 @@ def conv_layer_backward_impl(xs, ws, ts, gouts, needs, spec):
         gs.append(None if g is None else act_backward(ts[j], g.contiguous(), act, param))
     B = xs[0].shape[0]
     grads = [xs[0].new_empty(0) for _ in range(n_in + ne + nb)]   # distinct: op outputs may not alias
+    added = {i: j for j, i in parse_conv_adds(spec).items()}
     for i in range(n_in):
         if not needs[i]:
+            continue
+        if i in added:   # the addend's gradient is the pre-activation gradient itself (a copy: outputs may not alias)
+            g = gs[added[i]]
+            grads[i] = torch.zeros_like(xs[i]) if g is None else g.clone()
             continue
         es = [(e, edges[e]) for e in range(ne) if edges[e][1] == i and gs[edges[e][0]] is not None]
         x = xs[i]
@@ -321,9 +344,10 @@ def conv_layer_backward_impl(xs, ws, ts, gouts, needs, spec):
     return grads
 
 
-def conv_layer(B, outs, edges, inputs):
+def conv_layer(B, outs, edges, inputs, adds=None):
     """the ffc::conv_layer op over modules: edges (out j, input i, Seg, module) whose weight / bias
-    are the parameters (spectral norm refreshed first, as the module call would)"""
+    are the parameters (spectral norm refreshed first, as the module call would); adds [(out j, input i)]:
+    inputs added to an output before its activation"""
     spec_edges, ws, bs = [], [], []
     for j, i, sg, m in edges:
         rt.sn_refresh_train(m)
@@ -333,16 +357,18 @@ def conv_layer(B, outs, edges, inputs):
             bs.append(m.bias)
         spec_edges.append((j, i, sg, 1 if isinstance(m, nn.ConvTranspose2d) else 0, b))
         ws.append(m.weight)
-    ys = torch.ops.ffc.conv_layer(list(inputs), ws, bs, conv_spec(outs, spec_edges))
+    ys = torch.ops.ffc.conv_layer(list(inputs), ws, bs, conv_spec(outs, spec_edges, adds))
     return ys[:len(outs)]
 
 
 # --------------------------------------------------------------------------- BatchNorm2d + activation
-def bn_act_impl(x, gamma, beta, running_mean, running_var, use_batch, eps, act, param):
+def bn_act_impl(x, gamma, beta, running_mean, running_var, use_batch, eps, act, param, up=False):
     """ffc::bn_act: y = act(BN(x)) with nn.BatchNorm2d's normalisation (batch statistics when
     use_batch, else the running ones).  -> [y, scale, shift, stats]: stats = the fp64 batch moments
     [C][3] {n, sum x, sum x^2} (all-reduced under SyncBN) with batch statistics, the running
-    (mean, var) [2][C] otherwise -- the backward's input and ffc::bn_update_running's"""
+    (mean, var) [2][C] otherwise -- the backward's input and ffc::bn_update_running's.
+    ``up`` (ffc::bn_act_up2b): y = the bilinear x2 upsample of act(BN(x)) (ffc_act_up2b; act(BN(x)) itself is
+    not written)"""
     x = rt.require(x, "x")
     B, C = x.shape[:2]
     HW = x[0, 0].numel()
@@ -369,6 +395,8 @@ def bn_act_impl(x, gamma, beta, running_mean, running_var, use_batch, eps, act, 
         stats = torch.stack((running_mean.detach(), running_var.detach()))
         check(L.ffc_bn_finalize(None, C, ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), None, 0, 0, 0.1,
                                 float(eps), 1.0, ptr(scale), ptr(shift), stream), "ffc_bn_finalize")
+    if up:
+        return [act_up2b(x, scale, shift, False, act, param), scale, shift, stats]
     y = torch.empty_like(x)
     with rt.observe("bn_act", bytes=8.0 * x.numel()):
         check(L.ffc_bn_act_apply(ptr(x), ptr(y), B, C, HW, ptr(scale), ptr(shift), act, float(param), stream),
@@ -518,6 +546,118 @@ def up2_impl(x, scale):
     B, C, h, w = x.shape
     y = torch.empty((B, C, 2 * h, 2 * w), device=x.device, dtype=torch.float32)
     check(rt.lib().ffc_up2(ptr(x), B * C, h, w, float(scale), ptr(y), _stream(x)), "ffc_up2")
+    return y
+
+
+def act_impl(x, act, param):
+    """ffc::act: y = act(x) out of place (ReLU .. Sigmoid: the backward reads the output).  DBlock's leading
+    nn.ReLU(True) without touching the caller's tensor"""
+    x = rt.require(x, "x")
+    if x.dim() != 4 or not 1 <= act <= 4:
+        raise NotImplementedError(f"ffc::act: a (B, C, H, W) tensor and ReLU / LeakyReLU / Tanh / Sigmoid, got "
+                                  f"{tuple(x.shape)}, act {act}")
+    return _act_out(x, act, param, _stream(x))
+
+
+def act_up2b(x, scale, shift, per_sample, act, param):
+    """up2_bilinear(act(scale * x + shift)) on ffc_act_up2b (x dense NCHW on the GPU; scale / shift (C), (B, C)
+    with per_sample, or None)"""
+    B, C, h, w = x.shape
+    y = torch.empty((B, C, 2 * h, 2 * w), device=x.device, dtype=torch.float32)
+    with rt.observe("act_up2b", bytes=20.0 * x.numel()):
+        check(rt.lib().ffc_act_up2b(ptr(x), ptr(scale), ptr(shift), 1 if per_sample else 0, B, C, h, w, int(act),
+                                    float(param), ptr(y), _stream(x)), "ffc_act_up2b")
+    return y
+
+
+def up2_bilinear_impl(x, scale, shift, act, param):
+    """ffc::up2_bilinear: F.interpolate(act(scale * x + shift), scale_factor=2, mode='bilinear',
+    align_corners=False); scale / shift: (C,) per channel, (B, C) per sample and channel, or None"""
+    x = rt.require(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"up2_bilinear: x must be (B, C, h, w), got {tuple(x.shape)}")
+    B, C = x.shape[:2]
+    if (scale is None) != (shift is None):
+        raise RuntimeError("up2_bilinear: scale and shift go together")
+    per_sample = False
+    if scale is not None:
+        scale, shift = rt.require(scale, "scale"), rt.require(shift, "shift")
+        if tuple(scale.shape) != tuple(shift.shape) or tuple(scale.shape) not in ((C,), (B, C)):
+            raise RuntimeError(f"up2_bilinear: scale / shift must be ({C},) or ({B}, {C}), got "
+                               f"{tuple(scale.shape)} / {tuple(shift.shape)}")
+        per_sample = scale.dim() == 2
+    return act_up2b(x, scale, shift, per_sample, act, param)
+
+
+def up2_bilinear_adjoint_impl(dy):
+    """ffc::up2_bilinear_adjoint: the transpose of the plain bilinear x2 upsample, (B, C, 2h, 2w) -> (B, C, h, w)"""
+    dy = rt.require(dy, "dy")
+    if dy.dim() != 4 or dy.shape[2] % 2 or dy.shape[3] % 2:
+        raise RuntimeError(f"up2_bilinear_adjoint: dy must be (B, C, 2h, 2w), got {tuple(dy.shape)}")
+    B, C, H, W = dy.shape
+    dx = torch.empty((B, C, H // 2, W // 2), device=dy.device, dtype=torch.float32)
+    with rt.observe("up2b_adjoint", bytes=5.0 * dy.numel()):
+        check(rt.lib().ffc_up2b_adjoint(ptr(dy), B * C, H // 2, W // 2, ptr(dx), _stream(dy)), "ffc_up2b_adjoint")
+    return dx
+
+
+def pool2_act_impl(x, act, param):
+    """ffc::pool2_act: act(AvgPool2d(2)(x)) in one pass (a down-sampling DBlock's output, activated for the next
+    block)"""
+    x = rt.require(x, "x")
+    B, C, H, W = x.shape
+    if H % 2 or W % 2:
+        raise NotImplementedError("AvgPool2d(2) downsample of an odd-sized input")
+    y = torch.empty((B, C, H // 2, W // 2), device=x.device, dtype=torch.float32)
+    with rt.observe("pool2_act", bytes=5.0 * x.numel()):
+        check(rt.lib().ffc_pool2_act(ptr(x), B * C, H, W, int(act), float(param), ptr(y), _stream(x)),
+              "ffc_pool2_act")
+    return y
+
+
+def pool2_act_backward_impl(y, dy, act, param):
+    """ffc::pool2_act_backward: dx = nearest x2 of 0.25 * dy * act'(y), y the op's output"""
+    y, dy = y.contiguous(), rt.require(dy, "dy")
+    B, C, h, w = y.shape
+    dx = torch.empty((B, C, 2 * h, 2 * w), device=y.device, dtype=torch.float32)
+    with rt.observe("pool2_act_bwd", bytes=24.0 * y.numel()):
+        check(rt.lib().ffc_pool2_act_bwd(ptr(y), ptr(dy), B * C, h, w, int(act), float(param), ptr(dx), _stream(y)),
+              "ffc_pool2_act_bwd")
+    return dx
+
+
+def relu_sum_pool_impl(x):
+    """ffc::relu_sum_pool: torch.sum(relu(x), (2, 3)) -> (B, C) (fgan128_complete.py:432-435)"""
+    x = rt.require(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"relu_sum_pool: x must be (B, C, H, W), got {tuple(x.shape)}")
+    B, C, H, W = x.shape
+    out = torch.empty((B, C), device=x.device, dtype=torch.float32)
+    with rt.observe("relu_sum_pool", bytes=4.0 * x.numel()):
+        check(rt.lib().ffc_relu_sum_pool(ptr(x), B * C, H * W, ptr(out), _stream(x)), "ffc_relu_sum_pool")
+    return out
+
+
+def relu_sum_pool_backward_impl(x, dout):
+    """ffc::relu_sum_pool_backward: dx = (x > 0) * dout[b, c]"""
+    x, dout = x.contiguous(), rt.require(dout, "dout")
+    B, C, H, W = x.shape
+    dx = torch.empty_like(x)
+    with rt.observe("relu_sum_pool_bwd", bytes=8.0 * x.numel()):
+        check(rt.lib().ffc_relu_sum_pool_bwd(ptr(x), ptr(dout), B * C, H * W, ptr(dx), _stream(x)),
+              "ffc_relu_sum_pool_bwd")
+    return dx
+
+
+def bn_act_up2b(bn: nn.BatchNorm2d, x, act=(0, 0.0)):
+    """bilinear x2 upsample of BatchNorm2d ``bn`` + activation on the ffc::bn_act_up2b op (GBlock's b1 -> ReLU ->
+    F.interpolate, fgan128_complete.py:148-165), then the running-statistics update in training mode"""
+    use_batch, update = rt.bn_mode(bn)
+    y, _, _, stats = torch.ops.ffc.bn_act_up2b(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch,
+                                               float(bn.eps), int(act[0]), float(act[1]))
+    if update:
+        torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked, stats,
+                                        -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
     return y
 
 

@@ -281,6 +281,13 @@ SIGNATURES = [
                                c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     ("ffc_aw_combine", c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                ctypes.POINTER(c_longlong), c_int, c_void_p, c_int, c_void_p]),
+    ("ffc_act_up2b", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
+                             c_void_p, c_void_p]),
+    ("ffc_up2b_adjoint", c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_pool2_act", c_int, [c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("ffc_pool2_act_bwd", c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
+    ("ffc_relu_sum_pool", c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
+    ("ffc_relu_sum_pool_bwd", c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
 ]
 
 _lock = threading.Lock()

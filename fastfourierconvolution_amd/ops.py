@@ -18,6 +18,10 @@ Training ops (autograd): one per op the reference's forward is made of (see _aut
   ffc::lfu_split       quadrant stack of the local Fourier unit (spectral_transform.py:96-101, a comment
                        there; run with set_lfu)                     backward: ffc::lfu_split_backward
   ffc::lfu_tile_add    v + its output repeated 2 x 2 (:104-108)     backward: ffc::lfu_tile_backward
+  ffc::up2_bilinear, ffc::bn_act_up2b   bilinear x2 upsample [of BatchNorm2d + activation] (GBlock,
+                       fgan128_complete.py:148-165)                 backward: ffc::up2_bilinear_adjoint [+ bn_act_backward]
+  ffc::pool2_act, ffc::act, ffc::relu_sum_pool   DBlock's pooling + ReLU and the critic's global sum pooling
+                       (fgan128_complete.py:249-278, :432-435)      backward: ffc::*_backward
 
 Inference ops (the fused kernels; used under torch.no_grad() / when nothing needs a gradient):
   ffc::ffc_bn_act      one FFC_BN_ACT / FFC / FFCTranspose layer (ffc_bn_act.py:70-83, ffc.py:84-99,
@@ -251,6 +255,176 @@ def _scale_setup(ctx, inputs, output):
 
 pool2.register_autograd(lambda ctx, dy: (torch.ops.ffc.up2(dy, ctx.scale), None), setup_context=_scale_setup)
 up2.register_autograd(lambda ctx, dy: (torch.ops.ffc.pool2(dy, ctx.scale), None), setup_context=_scale_setup)
+
+# ---------------------------------------------------------------- ffc::up2_bilinear (+ adjoint), ffc::bn_act_up2b
+# F.interpolate(scale_factor=2, mode='bilinear', align_corners=False) of GBlock (fgan128_complete.py:148-156)
+
+
+@torch.library.custom_op("ffc::up2_bilinear", mutates_args=())
+def up2_bilinear(x: Tensor, scale: Optional[Tensor], shift: Optional[Tensor], act: int, act_param: float) -> Tensor:
+    """up2(act(scale * x + shift)); scale / shift (C,), (B, C) or None.  Differentiable in its plain form (no
+    affine, Identity); the BatchNorm form with a backward is ffc::bn_act_up2b"""
+    return ag.up2_bilinear_impl(x, scale, shift, act, act_param)
+
+
+@up2_bilinear.register_fake
+def _(x, scale, shift, act, act_param):
+    return x.new_empty((x.shape[0], x.shape[1], 2 * x.shape[2], 2 * x.shape[3]))
+
+
+@torch.library.custom_op("ffc::up2_bilinear_adjoint", mutates_args=())
+def up2_bilinear_adjoint(dy: Tensor) -> Tensor:
+    return ag.up2_bilinear_adjoint_impl(dy)
+
+
+@up2_bilinear_adjoint.register_fake
+def _(dy):
+    return dy.new_empty((dy.shape[0], dy.shape[1], dy.shape[2] // 2, dy.shape[3] // 2))
+
+
+def _up2b_setup(ctx, inputs, output):
+    _, scale, _, act, _ = inputs
+    ctx.plain = scale is None and act == 0
+
+
+def _up2b_bwd(ctx, dy):
+    if not ctx.plain:
+        raise NotImplementedError("ffc::up2_bilinear has a backward in its plain form only (ffc::bn_act_up2b "
+                                  "differentiates the BatchNorm + activation form)")
+    return torch.ops.ffc.up2_bilinear_adjoint(dy), None, None, None, None
+
+
+up2_bilinear.register_autograd(_up2b_bwd, setup_context=_up2b_setup)
+up2_bilinear_adjoint.register_autograd(lambda ctx, g: torch.ops.ffc.up2_bilinear(g, None, None, 0, 0.0),
+                                       setup_context=lambda ctx, inputs, output: None)
+
+
+@torch.library.custom_op("ffc::bn_act_up2b", mutates_args=())
+def bn_act_up2b(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], running_mean: Optional[Tensor],
+                running_var: Optional[Tensor], use_batch: bool, eps: float, act: int, act_param: float) -> List[Tensor]:
+    """ffc::bn_act with the bilinear x2 upsample applied to its output: [y (B, C, 2h, 2w), scale, shift, stats]"""
+    return ag.bn_act_impl(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param, up=True)
+
+
+@bn_act_up2b.register_fake
+def _(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param):
+    C = x.shape[1]
+    stats = x.new_empty((C, 3), dtype=torch.float64) if use_batch else x.new_empty((2, C))
+    return [x.new_empty((x.shape[0], C, 2 * x.shape[2], 2 * x.shape[3])), x.new_empty(C), x.new_empty(C), stats]
+
+
+def _bn_act_up2b_bwd(ctx, grads):
+    """the adjoint upsample brings dy to the low resolution, where it is ffc::bn_act's backward (x, scale and shift
+    are what that needs)"""
+    if grads[0] is None:
+        return (None,) * 9
+    return _bn_act_bwd(ctx, [torch.ops.ffc.up2_bilinear_adjoint(grads[0])])
+
+
+bn_act_up2b.register_autograd(_bn_act_up2b_bwd, setup_context=_bn_act_setup)
+
+# ---------------------------------------------------------------- ffc::pool2_act, ffc::relu_sum_pool (DBlock, critic)
+
+
+@torch.library.custom_op("ffc::pool2_act", mutates_args=())
+def pool2_act(x: Tensor, act: int, act_param: float) -> Tensor:
+    """act(AvgPool2d(2)(x)) (act: Identity, ReLU, LeakyReLU, Tanh, Sigmoid)"""
+    return ag.pool2_act_impl(x, act, act_param)
+
+
+@pool2_act.register_fake
+def _(x, act, act_param):
+    return x.new_empty((x.shape[0], x.shape[1], x.shape[2] // 2, x.shape[3] // 2))
+
+
+@torch.library.custom_op("ffc::pool2_act_backward", mutates_args=())
+def pool2_act_backward(y: Tensor, dy: Tensor, act: int, act_param: float) -> Tensor:
+    return ag.pool2_act_backward_impl(y, dy, act, act_param)
+
+
+@pool2_act_backward.register_fake
+def _(y, dy, act, act_param):
+    return y.new_empty((y.shape[0], y.shape[1], 2 * y.shape[2], 2 * y.shape[3]))
+
+
+def _pool2_act_setup(ctx, inputs, output):
+    ctx.cfg = (int(inputs[1]), float(inputs[2]))
+    ctx.save_for_backward(output)
+
+
+def _pool2_act_bwd(ctx, dy):
+    (y,) = ctx.saved_tensors
+    return torch.ops.ffc.pool2_act_backward(y, dy, *ctx.cfg), None, None
+
+
+pool2_act.register_autograd(_pool2_act_bwd, setup_context=_pool2_act_setup)
+
+
+@torch.library.custom_op("ffc::act", mutates_args=())
+def act(x: Tensor, act: int, act_param: float) -> Tensor:
+    """act(x) out of place (ReLU, LeakyReLU, Tanh, Sigmoid); backward: ffc_act_bwd through the output"""
+    return ag.act_impl(x, act, act_param)
+
+
+@act.register_fake
+def _(x, act, act_param):
+    return torch.empty_like(x)
+
+
+@torch.library.custom_op("ffc::act_backward", mutates_args=())
+def act_backward(y: Tensor, dy: Tensor, act: int, act_param: float) -> Tensor:
+    return ag.act_backward(y.contiguous(), dy, act, act_param)
+
+
+@act_backward.register_fake
+def _(y, dy, act, act_param):
+    return torch.empty_like(y)
+
+
+def _act_setup(ctx, inputs, output):
+    ctx.cfg = (int(inputs[1]), float(inputs[2]))
+    ctx.save_for_backward(output)
+
+
+def _act_bwd(ctx, dy):
+    (y,) = ctx.saved_tensors
+    return torch.ops.ffc.act_backward(y, dy, *ctx.cfg), None, None
+
+
+act.register_autograd(_act_bwd, setup_context=_act_setup)
+
+
+@torch.library.custom_op("ffc::relu_sum_pool", mutates_args=())
+def relu_sum_pool(x: Tensor) -> Tensor:
+    """torch.sum(relu(x), (2, 3)) -> (B, C)"""
+    return ag.relu_sum_pool_impl(x)
+
+
+@relu_sum_pool.register_fake
+def _(x):
+    return x.new_empty((x.shape[0], x.shape[1]))
+
+
+@torch.library.custom_op("ffc::relu_sum_pool_backward", mutates_args=())
+def relu_sum_pool_backward(x: Tensor, dout: Tensor) -> Tensor:
+    return ag.relu_sum_pool_backward_impl(x, dout)
+
+
+@relu_sum_pool_backward.register_fake
+def _(x, dout):
+    return torch.empty_like(x)
+
+
+def _rsp_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+
+
+def _rsp_bwd(ctx, dout):
+    (x,) = ctx.saved_tensors
+    return torch.ops.ffc.relu_sum_pool_backward(x, dout)
+
+
+relu_sum_pool.register_autograd(_rsp_bwd, setup_context=_rsp_setup)
 
 # ---------------------------------------------------------------- ffc::rfft2 / ffc::irfft2
 

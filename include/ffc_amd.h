@@ -853,6 +853,34 @@ int ffc_aw_weights(const float* const* g_real, const float* const* g_fake, const
 int ffc_aw_combine(const float* const* g_real, const float* const* g_fake, float* const* out, const long long* numel,
                    int n, const double* stats, int jobs_per_launch, void* stream);
 
+/* ------------------------------------------------------------------ ResNet SNGAN resampling
+ * The resampling steps of GBlock / DBlock and the critic's global sum pooling (fgan128_complete.py:75-438).
+ * fp32, dense NCHW planes; no atomics, every sum in one fixed order (bitwise reproducible); any base alignment
+ * (16- / 8-byte accesses only where the pointer allows them).  Every entry point returns FFC_E_INVALID without a
+ * launch for a null pointer, a plane side <= 0 and a tensor of more than 2^31 - 1 elements.  Pure additions: the
+ * ABI version is unchanged. */
+/* y (B, C, 2h, 2w) = up2(act(scale * x + shift)), up2 = F.interpolate(scale_factor=2, mode='bilinear',
+ * align_corners=False): along an axis of length n, with indices clamped to [0, n-1],
+ *   Y[2i] = 0.25 X[i-1] + 0.75 X[i]      Y[2i+1] = 0.75 X[i] + 0.25 X[i+1]
+ * (h = 1 or w = 1 replicates).  scale / shift: (C) floats (ffc_bn_finalize's), or with per_sample (B, C) floats
+ * (the rows a conditional BatchNorm gathers), or both NULL (no affine; act still applies).  The activation is
+ * applied at the low resolution, which is never written. */
+int ffc_act_up2b(const float* x, const float* scale, const float* shift, int per_sample, int B, int C, int h, int w,
+                 int act, float act_param, float* y, void* stream);
+/* dx (P, h, w) = up2^T dy (P, 2h, 2w): dx[i][j] gathers weights (0.25, 0.75, 0.75, 0.25) per axis from dy rows /
+ * columns 2i-1 .. 2i+2 clamped to the plane, so the edge pixels collect the clamped taps' weights */
+int ffc_up2b_adjoint(const float* dy, long long P, int h, int w, float* dx, void* stream);
+/* y (P, H/2, W/2) = act(0.25 * 2x2 sum) (H, W even; act: Identity .. Sigmoid), and its backward from the output:
+ * dx (P, 2h, 2w) = nearest x2 of 0.25 * dy * act'(y) */
+int ffc_pool2_act(const float* x, long long P, int H, int W, int act, float act_param, float* y, void* stream);
+int ffc_pool2_act_bwd(const float* y, const float* dy, long long P, int h, int w, int act, float act_param, float* dx,
+                      void* stream);
+/* out[p] = sum over the HW elements of plane p of relu(x) (torch.sum(relu(h), (2, 3))); planes of up to 32
+ * elements are summed in index order by one thread, larger ones by one wave (lane l: l, l + 64, ..., then a
+ * butterfly).  Backward: dx = (x > 0) * dout[p] */
+int ffc_relu_sum_pool(const float* x, long long P, int HW, float* out, void* stream);
+int ffc_relu_sum_pool_bwd(const float* x, const float* dout, long long P, int HW, float* dx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
