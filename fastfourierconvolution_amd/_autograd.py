@@ -167,16 +167,26 @@ def conv_wgrad(U, V, k, s, p, d, dW_shape):
     return dW
 
 
+def reduce_ws(x):
+    """the split count (ffc_reduce_splits) of the per-channel reductions over x (B, C, ...) and their fp64 workspace"""
+    B, C = x.shape[:2]
+    S = rt.lib().ffc_reduce_splits(B, C, x[0, 0].numel())
+    return S, torch.empty(S * C * 2, device=x.device, dtype=torch.float64)
+
+
+def channel_moments(x):
+    """fp64 raw moments [C][3] {n, sum x, sum x^2} of x (B, C, ...) per channel (ffc_channel_moments)"""
+    B, C = x.shape[:2]
+    S, ws = reduce_ws(x)
+    mom = torch.empty((C, 3), device=x.device, dtype=torch.float64)
+    check(rt.lib().ffc_channel_moments(ptr(x), B, C, x[0, 0].numel(), ptr(ws), S, ptr(mom), _stream(x)),
+          "ffc_channel_moments")
+    return mom
+
+
 def channel_sum(g):
     """sum over (B, H, W) per channel (bias gradient)"""
-    B, C = g.shape[:2]
-    HW = g[0, 0].numel()
-    L = rt.lib()
-    S = L.ffc_reduce_splits(B, C, HW)
-    ws = torch.empty(S * C * 2, device=g.device, dtype=torch.float64)
-    mom = torch.empty((C, 3), device=g.device, dtype=torch.float64)
-    check(L.ffc_channel_moments(ptr(g), B, C, HW, ptr(ws), S, ptr(mom), _stream(g)), "ffc_channel_moments")
-    return mom[:, 1].float()
+    return channel_moments(g)[:, 1].float()
 
 
 # --------------------------------------------------------------------------- conv layer (ffc::conv_layer)
@@ -362,6 +372,30 @@ def conv_layer(B, outs, edges, inputs, adds=None):
 
 
 # --------------------------------------------------------------------------- BatchNorm2d + activation
+def bn_normalize(x, gamma, beta, running_mean, running_var, use_batch, eps, sync):
+    """nn.BatchNorm2d's normalisation of x (B, C, H, W) folded to (scale, shift), from the batch statistics when
+    use_batch, else from the running ones; gamma / beta may be None.  -> (scale, shift, stats): stats = the fp64
+    batch moments [C][3] {n, sum x, sum x^2} (with ``sync``: all-reduced when a SyncBN group is active), or the
+    running (mean, var) [2][C]"""
+    C = x.shape[1]
+    scale = torch.empty(C, device=x.device, dtype=torch.float32)
+    shift = torch.empty(C, device=x.device, dtype=torch.float32)
+    if use_batch:
+        with rt.observe("bn_moments", bytes=4.0 * x.numel()):
+            stats = channel_moments(x)
+        grp = rt._sync_group() if sync else None   # SyncBN: global-batch statistics (SURVEY §8f)
+        if grp is not None:
+            from .distributed import merge_moments
+            merge_moments(stats, group=grp)
+        running = (None, None)
+    else:
+        stats = torch.stack((running_mean.detach(), running_var.detach())).float().contiguous()
+        running = (ptr(stats[0]), ptr(stats[1]))
+    rt.bn_finalize(rt.BnArgs(C, ptr(gamma), ptr(beta), *running, None, 0, 0.1, float(eps), 1.0),
+                   stats if use_batch else None, scale, shift, _stream(x))
+    return scale, shift, stats
+
+
 def bn_act_impl(x, gamma, beta, running_mean, running_var, use_batch, eps, act, param, up=False):
     """ffc::bn_act: y = act(BN(x)) with nn.BatchNorm2d's normalisation (batch statistics when
     use_batch, else the running ones).  -> [y, scale, shift, stats]: stats = the fp64 batch moments
@@ -375,32 +409,13 @@ def bn_act_impl(x, gamma, beta, running_mean, running_var, use_batch, eps, act, 
     n_feat = running_mean.numel() if running_mean is not None else (gamma.numel() if gamma is not None else C)
     if n_feat != C:
         raise RuntimeError(f"running_mean should contain {C} elements not {n_feat}")
-    grp = rt._sync_group() if use_batch else None   # SyncBN: global-batch statistics
-    L = rt.lib()
-    dev, stream = x.device, _stream(x)
-    scale = torch.empty(C, device=dev, dtype=torch.float32)
-    shift = torch.empty(C, device=dev, dtype=torch.float32)
-    if use_batch:
-        S = L.ffc_reduce_splits(B, C, HW)
-        ws = torch.empty(S * C * 2, device=dev, dtype=torch.float64)
-        stats = torch.empty((C, 3), device=dev, dtype=torch.float64)
-        with rt.observe("bn_moments", bytes=4.0 * x.numel()):
-            check(L.ffc_channel_moments(ptr(x), B, C, HW, ptr(ws), S, ptr(stats), stream), "ffc_channel_moments")
-        if grp is not None:
-            from .distributed import merge_moments
-            merge_moments(stats, group=grp)
-        check(L.ffc_bn_finalize(ptr(stats), C, ptr(gamma), ptr(beta), None, None, None, 1, 0, 0.1, float(eps), 1.0,
-                                ptr(scale), ptr(shift), stream), "ffc_bn_finalize")
-    else:
-        stats = torch.stack((running_mean.detach(), running_var.detach()))
-        check(L.ffc_bn_finalize(None, C, ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), None, 0, 0, 0.1,
-                                float(eps), 1.0, ptr(scale), ptr(shift), stream), "ffc_bn_finalize")
+    scale, shift, stats = bn_normalize(x, gamma, beta, running_mean, running_var, use_batch, eps, sync=True)
     if up:
         return [act_up2b(x, scale, shift, False, act, param), scale, shift, stats]
     y = torch.empty_like(x)
     with rt.observe("bn_act", bytes=8.0 * x.numel()):
-        check(L.ffc_bn_act_apply(ptr(x), ptr(y), B, C, HW, ptr(scale), ptr(shift), act, float(param), stream),
-              "ffc_bn_act_apply")
+        check(rt.lib().ffc_bn_act_apply(ptr(x), ptr(y), B, C, HW, ptr(scale), ptr(shift), act, float(param),
+                                        _stream(x)), "ffc_bn_act_apply")
     return [y, scale, shift, stats]
 
 
@@ -408,9 +423,17 @@ def bn_update_running_impl(running_mean, running_var, num_batches_tracked, stats
     """ffc::bn_update_running: running stats <- batch moments (unbiased variance), nn.BatchNorm2d's rule"""
     C = running_mean.numel()
     scratch = torch.empty(2 * C, device=running_mean.device, dtype=torch.float32)
-    check(rt.lib().ffc_bn_finalize(ptr(stats), C, None, None, ptr(running_mean), ptr(running_var),
-                                   ptr(num_batches_tracked), 1, 1, float(momentum), 1e-5, float(count_mult),
-                                   ptr(scratch), ptr(scratch[C:]), _stream(running_mean)), "ffc_bn_finalize")
+    rt.bn_finalize(rt.BnArgs(C, None, None, ptr(running_mean), ptr(running_var), ptr(num_batches_tracked), 1,
+                             float(momentum), 1e-5, float(count_mult)),
+                   stats, scratch, scratch[C:], _stream(running_mean))
+
+
+def update_running(bn: nn.BatchNorm2d, stats):
+    """nn.BatchNorm2d's running-statistics update of ``bn`` from the batch moments ``stats`` an op returned
+    (ffc::bn_update_running), in training mode with tracked statistics only"""
+    if rt.bn_mode(bn)[1]:
+        torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked, stats,
+                                        rt.bn_momentum(bn), 1.0)
 
 
 def bn_act_backward_impl(x, dy, scale, shift, stats, gamma, use_batch, sync, eps, act, param, need_dx, has_gamma,
@@ -423,8 +446,7 @@ def bn_act_backward_impl(x, dy, scale, shift, stats, gamma, use_batch, sync, eps
     B, C = x.shape[:2]
     HW = x[0, 0].numel()
     L = rt.lib()
-    S = L.ffc_reduce_splits(B, C, HW)
-    ws = torch.empty(S * C * 2, device=x.device, dtype=torch.float64)
+    S, ws = reduce_ws(x)
     coef = torch.empty(C * 3, device=x.device, dtype=torch.float32)
     dgamma = torch.empty(C, device=x.device, dtype=torch.float32) if has_gamma else None
     dbeta = torch.empty(C, device=x.device, dtype=torch.float32) if has_beta else None
@@ -466,12 +488,9 @@ RECORD = None   # tests: a list collecting every BN + activation output (kink pa
 def bn_act(bn: nn.BatchNorm2d, x, act=(0, 0.0)):
     """BatchNorm2d ``bn`` + activation on the ffc::bn_act op (the module's tensors as arguments), then
     the running-statistics update in training mode (ffc::bn_update_running)"""
-    use_batch, update = rt.bn_mode(bn)
-    y, _, _, stats = torch.ops.ffc.bn_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch,
+    y, _, _, stats = torch.ops.ffc.bn_act(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, rt.bn_mode(bn)[0],
                                           float(bn.eps), int(act[0]), float(act[1]))
-    if update:
-        torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked, stats,
-                                        -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
+    update_running(bn, stats)
     if RECORD is not None:
         RECORD.append(y.detach())
     return y
@@ -652,12 +671,9 @@ def relu_sum_pool_backward_impl(x, dout):
 def bn_act_up2b(bn: nn.BatchNorm2d, x, act=(0, 0.0)):
     """bilinear x2 upsample of BatchNorm2d ``bn`` + activation on the ffc::bn_act_up2b op (GBlock's b1 -> ReLU ->
     F.interpolate, fgan128_complete.py:148-165), then the running-statistics update in training mode"""
-    use_batch, update = rt.bn_mode(bn)
-    y, _, _, stats = torch.ops.ffc.bn_act_up2b(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, use_batch,
-                                               float(bn.eps), int(act[0]), float(act[1]))
-    if update:
-        torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked, stats,
-                                        -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
+    y, _, _, stats = torch.ops.ffc.bn_act_up2b(x, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                               rt.bn_mode(bn)[0], float(bn.eps), int(act[0]), float(act[1]))
+    update_running(bn, stats)
     return y
 
 
@@ -720,14 +736,19 @@ def linear(lin: nn.Linear, z):
 
 
 # --------------------------------------------------------------------------- Self_Attn
+def _attn_supported(B, C, H, W, what):
+    """NotImplementedError when the attention kernels refuse the shape; ``what`` leads the message, up to the shape"""
+    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
+        raise NotImplementedError(f"{what} {(B, C, H, W)}: the HIP attention kernels take "
+                                  "C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+
+
 def _attn_dims(x, qkv, what):
     """(B, C, H, W, d) of a Self_Attn call; NotImplementedError naming the shape when the kernels refuse it"""
     if x.dim() != 4:
         raise NotImplementedError(f"{what}: x must be (B, C, H, W), got {tuple(x.shape)}")
     B, C, H, W = x.shape
-    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
-        raise NotImplementedError(f"{what}: unsupported shape {tuple(x.shape)}: the HIP attention kernels take "
-                                  "C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+    _attn_supported(B, C, H, W, f"{what}: unsupported shape")
     d = C // 8
     if tuple(qkv.shape) != (B, 2 * d + C, H, W):
         raise RuntimeError(f"{what}: the stacked projection must be {(B, 2 * d + C, H, W)}, got {tuple(qkv.shape)}")
@@ -779,9 +800,7 @@ def self_attn_matrix_impl(qkv, L, C):
     if qkv.dim() != 4:
         raise RuntimeError(f"{what}: qkv must be 4-D (B, 2d + C, H, W), got {tuple(qkv.shape)}")
     B, M, H, W = qkv.shape
-    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
-        raise NotImplementedError(f"{what}: unsupported shape (B, C, H, W) = {(B, C, H, W)}: the HIP attention "
-                                  "kernels take C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+    _attn_supported(B, C, H, W, f"{what}: unsupported shape (B, C, H, W) =")
     d, N = C // 8, H * W
     if M != 2 * d + C:
         raise RuntimeError(f"{what}: the stacked projection of C = {C} must be {(B, 2 * d + C, H, W)}, got "
@@ -849,9 +868,7 @@ def self_attn(mod, x):
     B, C, H, W = x.shape
     if C != mod.chanel_in:
         raise RuntimeError(f"Self_Attn has {mod.chanel_in} channels, tensor has {C}")
-    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
-        raise NotImplementedError(f"Self_Attn: unsupported shape {tuple(x.shape)}: the HIP attention kernels take "
-                                  "C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+    _attn_supported(B, C, H, W, "Self_Attn: unsupported shape")
     grad = wants_grad(mod, x)
     M = 2 * (C // 8) + C
     (qkv,) = conv_layer(B, [(M, 0, 0.0)], [(0, 0, _plan.Seg("pw", C, H, W), _StackedQKV(mod, grad))], [x])
@@ -981,12 +998,17 @@ def spectral_v(st, x):
 
 
 # --------------------------------------------------------------------------- class-conditional fgan128
-def _labels(labels, B, what):
-    """class labels as the kernels read them: an int64 device tensor (B,) (never read on the host)"""
+def _label_tensor(labels, what):
+    """class labels are a tensor on the device (never read on the host)"""
     if not isinstance(labels, torch.Tensor):
         raise TypeError(f"{what}: labels must be a tensor, got {type(labels).__name__}")
     if not labels.is_cuda:
         raise FFCError(f"{what}: labels must be on a ROCm/HIP device (there is no CPU fallback)")
+
+
+def _labels(labels, B, what):
+    """class labels as the kernels read them: an int64 device tensor (B,)"""
+    _label_tensor(labels, what)
     if labels.dtype != torch.int64 or labels.dim() != 1 or labels.shape[0] != B:
         raise RuntimeError(f"{what}: labels must be int64 of shape ({B},), got {labels.dtype} {tuple(labels.shape)}")
     return labels.contiguous()
@@ -1044,9 +1066,8 @@ def cond_stem_impl(z, labels, embed, w_in, b_in, w_label, b_label, gamma_in, bet
         stats = torch.stack((torch.cat((rmean_in.detach(), rmean_label.detach())),
                              torch.cat((rvar_in.detach(), rvar_label.detach())))).float().contiguous()
         for k, (g, b) in enumerate(((gamma_in, beta_in), (gamma_label, beta_label))):
-            check(L.ffc_bn_finalize(None, C, ptr(g), ptr(b), ptr(stats[0, k * C:]), ptr(stats[1, k * C:]), None, 0, 0,
-                                    0.1, float(eps), 1.0, ptr(scale[k * C:]), ptr(shift[k * C:]), stream),
-                  "ffc_bn_finalize")
+            rt.bn_finalize(rt.BnArgs(C, ptr(g), ptr(b), ptr(stats[0, k * C:]), ptr(stats[1, k * C:]), None, 0, 0.1,
+                                     float(eps), 1.0), None, scale[k * C:], shift[k * C:], stream)
     y = torch.empty_like(pre)
     from ._lib import BnApplyItem
     item = (BnApplyItem * 1)()
@@ -1129,29 +1150,14 @@ def cbn_act_impl(x, labels, embed, running_mean, running_var, use_batch, eps, ac
         if tuple(noise.shape) != (B, 1) + tuple(x.shape[2:]) or noise_w.numel() != C:
             raise RuntimeError(f"cbn_act: noise must be {(B, 1) + tuple(x.shape[2:])} with {C} weights, got "
                                f"{tuple(noise.shape)} / {noise_w.numel()}")
-    L = rt.lib()
-    dev, stream = x.device, _stream(x)
-    scale = torch.empty(C, device=dev, dtype=torch.float32)
-    shift = torch.empty(C, device=dev, dtype=torch.float32)
-    if use_batch:
-        S = L.ffc_reduce_splits(B, C, HW)
-        ws = torch.empty(S * C * 2, device=dev, dtype=torch.float64)
-        stats = torch.empty((C, 3), device=dev, dtype=torch.float64)
-        with rt.observe("bn_moments", bytes=4.0 * x.numel()):
-            check(L.ffc_channel_moments(ptr(x), B, C, HW, ptr(ws), S, ptr(stats), stream), "ffc_channel_moments")
-        check(L.ffc_bn_finalize(ptr(stats), C, None, None, None, None, None, 1, 0, 0.1, float(eps), 1.0, ptr(scale),
-                                ptr(shift), stream), "ffc_bn_finalize")
-    else:
-        stats = torch.stack((running_mean.detach(), running_var.detach())).float().contiguous()
-        check(L.ffc_bn_finalize(None, C, None, None, ptr(stats[0]), ptr(stats[1]), None, 0, 0, 0.1, float(eps), 1.0,
-                                ptr(scale), ptr(shift), stream), "ffc_bn_finalize")
+    scale, shift, stats = bn_normalize(x, None, None, running_mean, running_var, use_batch, eps, sync=False)
     y = torch.empty_like(x)
     from ._lib import CbnApplyItem
     item = (CbnApplyItem * 1)()
     item[0] = CbnApplyItem(ptr(x), ptr(y), B, C, HW, embed.shape[0], ptr(scale), ptr(shift), ptr(embed), ptr(labels),
                            int(act), float(param), ptr(noise_w), ptr(noise))
     with rt.observe("cbn_act", bytes=8.0 * x.numel() + (4.0 * noise.numel() if noise is not None else 0.0)):
-        check(L.ffc_cbn_act_apply_batch(item, 1, stream), "ffc_cbn_act_apply_batch")
+        check(rt.lib().ffc_cbn_act_apply_batch(item, 1, _stream(x)), "ffc_cbn_act_apply_batch")
     return [y, scale, shift, stats]
 
 
@@ -1192,10 +1198,7 @@ def cbn_act_backward_impl(x, dy, labels, embed, scale, shift, use_batch, act, pa
 def cbn_labels(y, what="ConditionalBatchNorm2d"):
     """the reference's double torch.squeeze of the label argument (cond_bn.py:17-18) -> (B,) int64
     device labels; a 0-d result (B == 1) fails as the reference's chunk(2, 1) does"""
-    if not isinstance(y, torch.Tensor):
-        raise TypeError(f"{what}: labels must be a tensor, got {type(y).__name__}")
-    if not y.is_cuda:
-        raise FFCError(f"{what}: labels must be on a ROCm/HIP device (there is no CPU fallback)")
+    _label_tensor(y, what)
     y = torch.squeeze(torch.squeeze(y))
     if y.dim() == 0:
         raise IndexError("Dimension out of range (expected to be in range of [-1, 0], but got 1)")
@@ -1209,18 +1212,15 @@ def cbn_act(cbn, x, y, act=(0, 0.0), noise=None):
     if bn.weight is not None:
         raise NotImplementedError("ConditionalBatchNorm2d wraps an affine-less BatchNorm2d")
     labels = cbn_labels(y)
-    use_batch, update = rt.bn_mode(bn)
     nw = nz = None
     if noise is not None:
         mod, nz = noise
         if nz is None:
             nz = x.new_empty(x.shape[0], 1, x.shape[2], x.shape[3]).normal_()
         nw = mod.weight
-    out, _, _, stats = torch.ops.ffc.cbn_act(x, labels, cbn.embed.weight, bn.running_mean, bn.running_var, use_batch,
-                                             float(bn.eps), int(act[0]), float(act[1]), nw, nz)
-    if update:
-        torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked, stats,
-                                        -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
+    out, _, _, stats = torch.ops.ffc.cbn_act(x, labels, cbn.embed.weight, bn.running_mean, bn.running_var,
+                                             rt.bn_mode(bn)[0], float(bn.eps), int(act[0]), float(act[1]), nw, nz)
+    update_running(bn, stats)
     if RECORD is not None:
         RECORD.append(out.detach())
     return out
@@ -1239,16 +1239,13 @@ def cond_stem(mod, z, labels):
     modes = {rt.bn_mode(bn_i), rt.bn_mode(bn_l)}
     if len(modes) != 1 or bn_i.eps != bn_l.eps:
         raise NotImplementedError("cond_stem: both stem BatchNorms must be in the same mode, with the same eps")
-    use_batch, update = modes.pop()
+    use_batch, _ = modes.pop()
     y, _, _, _, stats = torch.ops.ffc.cond_stem(
         z, labels, mod.label_embed.weight, conv_i.weight, conv_i.bias, conv_l.weight, conv_l.bias, bn_i.weight,
         bn_i.bias, bn_l.weight, bn_l.bias, bn_i.running_mean, bn_i.running_var, bn_l.running_mean, bn_l.running_var,
         use_batch, float(bn_i.eps))
-    if update:
-        for k, bn in enumerate((bn_i, bn_l)):
-            torch.ops.ffc.bn_update_running(bn.running_mean, bn.running_var, bn.num_batches_tracked,
-                                            stats[k * STEM_CH:(k + 1) * STEM_CH],
-                                            -1.0 if bn.momentum is None else float(bn.momentum), 1.0)
+    for k, bn in enumerate((bn_i, bn_l)):
+        update_running(bn, stats[k * STEM_CH:(k + 1) * STEM_CH])
     return y
 
 

@@ -131,68 +131,97 @@ def bn_mode(bn: nn.BatchNorm2d):
     return use_batch, update
 
 
-def bn_scale_shift(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device, stream):
-    """-> (scale, shift) fp32 device tensors of length C, nn.BatchNorm2d semantics."""
+def bn_momentum(bn: nn.BatchNorm2d) -> float:
+    """the momentum as the library takes it: -1 for None (the cumulative average over num_batches_tracked)"""
+    return -1.0 if bn.momentum is None else float(bn.momentum)
+
+
+class BnArgs(NamedTuple):
+    """an nn.BatchNorm2d as the C calls take it: ``args[1:]`` are the nine arguments before the outputs of
+    ffc_bn_reduce_finalize and ffc_bn_finalize, and the same nine fields of ffc_bn_rf_item and ffc_bn_fold"""
+    C: int
+    gamma: Optional[int]
+    beta: Optional[int]
+    running_mean: Optional[int]
+    running_var: Optional[int]
+    num_batches_tracked: Optional[int]
+    update: int
+    momentum: float   # -1: None (the cumulative average)
+    eps: float
+    count_mult: float
+
+
+def bn_args(bn: nn.BatchNorm2d, C: int, count_mult: float, fold: bool = False) -> BnArgs:
+    """``bn`` over C channels as a BnArgs; RuntimeError when the module has another channel count.
+    The running-statistics pointers are given wherever the module has the buffers: the separate
+    finalize also reads them in eval mode.  ``fold`` (the record of an ffc_bn_fold, finalized inside
+    its consumer kernel) gives them only when they are updated: a fold always runs on batch statistics
+    and touches the buffers for nothing else, so its struct has carried them only then since the fold was
+    written.  The two rules are two options of this one function on purpose; do not unify them."""
     if bn.num_features != C:
         raise RuntimeError(f"running_mean should contain {C} elements not {bn.num_features}")
-    use_batch, update = bn_mode(bn)
-    L = lib()
+    _, update = bn_mode(bn)
+    stats = [None if t is None or (fold and not update) else ptr(t)
+             for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked)]
+    return BnArgs(C, ptr(bn.weight.detach()) if bn.weight is not None else None,
+                  ptr(bn.bias.detach()) if bn.bias is not None else None, *stats, int(update),
+                  bn_momentum(bn), float(bn.eps), float(count_mult))
+
+
+def bn_finalize(a: BnArgs, moments, scale, shift, stream):
+    """ffc_bn_finalize: (scale, shift) of ``a`` from the raw moments [C][3] {n, sum x, sum x^2}, or from
+    the running statistics when ``moments`` is None"""
+    check(lib().ffc_bn_finalize(ptr(moments), a.C, *a[1:6], int(moments is not None), *a[6:], ptr(scale), ptr(shift),
+                                stream), "ffc_bn_finalize")
+
+
+def _bn_reduce_synced(slab, nrows: int, C: int, device, stream, grp):
+    """the slab's raw moments by ffc_bn_reduce, all-reduced over ``grp`` (SyncBN) -> (the buffer, its [C][3] view)"""
+    from .distributed import merge_moments
+    # [C][3] moments + the large-slab scratch behind them (ffc_bn_reduce_ws_doubles)
+    mbuf = torch.empty(3 * C + lib().ffc_bn_reduce_ws_doubles(nrows, C), device=device, dtype=torch.float64)
+    moments = mbuf[:3 * C].view(C, 3)
+    check(lib().ffc_bn_reduce(ptr(slab), nrows, C, ptr(mbuf), stream), "ffc_bn_reduce")
+    merge_moments(moments, group=grp)
+    return mbuf, moments
+
+
+def bn_scale_shift(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device, stream):
+    """-> (scale, shift) fp32 device tensors of length C, nn.BatchNorm2d semantics."""
+    a = bn_args(bn, C, count_mult)
     scale = torch.empty(C, device=device, dtype=torch.float32)
     shift = torch.empty(C, device=device, dtype=torch.float32)
-    momentum = -1.0 if bn.momentum is None else float(bn.momentum)
-    gamma = ptr(bn.weight.detach()) if bn.weight is not None else None
-    beta = ptr(bn.bias.detach()) if bn.bias is not None else None
-    rm = ptr(bn.running_mean) if bn.running_mean is not None else None
-    rv = ptr(bn.running_var) if bn.running_var is not None else None
-    nbt = ptr(bn.num_batches_tracked) if bn.num_batches_tracked is not None else None
-    if use_batch:
-        # [C][3] moments + the large-slab scratch behind them (ffc_bn_reduce_ws_doubles)
-        mbuf = torch.empty(3 * C + L.ffc_bn_reduce_ws_doubles(nrows, C), device=device, dtype=torch.float64)
-        moments = mbuf[:3 * C].view(C, 3)
-        grp = _sync_group()
-        if grp is None:
-            with observe("bn_stats"):
-                check(L.ffc_bn_reduce_finalize(ptr(slab), nrows, C, ptr(mbuf), gamma, beta, rm, rv, nbt,
-                                               int(update), momentum, float(bn.eps), float(count_mult), ptr(scale),
-                                               ptr(shift), stream), "ffc_bn_reduce_finalize")
-        else:
-            from .distributed import merge_moments
-            with observe("bn_stats"):
-                check(L.ffc_bn_reduce(ptr(slab), nrows, C, ptr(mbuf), stream), "ffc_bn_reduce")
-                merge_moments(moments, group=grp)
-                check(L.ffc_bn_finalize(ptr(moments), C, gamma, beta, rm, rv, nbt, 1, int(update), momentum,
-                                        float(bn.eps), float(count_mult), ptr(scale), ptr(shift), stream),
-                      "ffc_bn_finalize")
+    if not bn_mode(bn)[0]:
+        bn_finalize(a, None, scale, shift, stream)
+        return scale, shift
+    grp = _sync_group()
+    if grp is None:
+        mbuf = torch.empty(3 * C + lib().ffc_bn_reduce_ws_doubles(nrows, C), device=device, dtype=torch.float64)
+        with observe("bn_stats"):
+            check(lib().ffc_bn_reduce_finalize(ptr(slab), nrows, C, ptr(mbuf), *a[1:], ptr(scale), ptr(shift), stream),
+                  "ffc_bn_reduce_finalize")
     else:
-        check(L.ffc_bn_finalize(None, C, gamma, beta, rm, rv, nbt, 0, 0, momentum, float(bn.eps), 1.0,
-                                ptr(scale), ptr(shift), stream), "ffc_bn_finalize")
+        with observe("bn_stats"):
+            _, moments = _bn_reduce_synced(slab, nrows, C, device, stream, grp)
+            bn_finalize(a, moments, scale, shift, stream)
     return scale, shift
 
 
 def _bn_finalize_batch(items, batch, device, stream):
     """single rank: the batch's reduce + finalize in one launch (ffc_bn_reduce_finalize_batch)"""
     from ._lib import BnRfItem
-    L = lib()
     arr = (BnRfItem * len(batch))()
     res, keep = {}, []
     for k, (bn, C, slab, nrows, cm) in enumerate(batch):
-        if bn.num_features != C:
-            raise RuntimeError(f"running_mean should contain {C} elements not {bn.num_features}")
-        _, update = bn_mode(bn)
+        a = bn_args(bn, C, cm)
         scale = torch.empty(C, device=device, dtype=torch.float32)
         shift = torch.empty(C, device=device, dtype=torch.float32)
-        mbuf = torch.empty(3 * C + L.ffc_bn_reduce_ws_doubles(nrows, C), device=device, dtype=torch.float64)
+        mbuf = torch.empty(3 * C + lib().ffc_bn_reduce_ws_doubles(nrows, C), device=device, dtype=torch.float64)
         keep.append(mbuf)
-        arr[k] = BnRfItem(ptr(slab), nrows, C, ptr(mbuf), ptr(bn.weight.detach()) if bn.weight is not None else None,
-                          ptr(bn.bias.detach()) if bn.bias is not None else None,
-                          ptr(bn.running_mean) if bn.running_mean is not None else None,
-                          ptr(bn.running_var) if bn.running_var is not None else None,
-                          ptr(bn.num_batches_tracked) if bn.num_batches_tracked is not None else None,
-                          int(update), -1.0 if bn.momentum is None else float(bn.momentum), float(bn.eps), float(cm),
-                          ptr(scale), ptr(shift))
+        arr[k] = BnRfItem(ptr(slab), nrows, C, ptr(mbuf), *a[1:], ptr(scale), ptr(shift))
         res[id(bn)] = (scale, shift)
     with observe("bn_stats"):
-        check(L.ffc_bn_reduce_finalize_batch(arr, len(batch), stream), "ffc_bn_reduce_finalize_batch")
+        check(lib().ffc_bn_reduce_finalize_batch(arr, len(batch), stream), "ffc_bn_reduce_finalize_batch")
     return [res[id(it[0])] if id(it[0]) in res else bn_scale_shift(it[0], it[1], it[2], it[3], it[4], device, stream)
             for it in items]
 
@@ -239,6 +268,7 @@ def bn_scale_shift_many(items, device, stream):
         return _bn_finalize_batch(items, batch, device, stream)
     from .distributed import merge_moments
     L = lib()
+    recs = [bn_args(bn, C, cm) for bn, C, _, _, cm in batch]
     Cs = [it[1] for it in batch]
     # moments of every BN back to back ([sum C][3]); each reduce's scratch lies behind its own
     # moments (the later BNs' moments included: they are reduced afterwards, in stream order)
@@ -247,25 +277,15 @@ def bn_scale_shift_many(items, device, stream):
     mbuf = torch.empty(need, device=device, dtype=torch.float64)
     with observe("bn_stats"):
         for (bn, C, slab, nrows, _), o in zip(batch, offs):
-            if bn.num_features != C:
-                raise RuntimeError(f"running_mean should contain {C} elements not {bn.num_features}")
             check(L.ffc_bn_reduce(ptr(slab), nrows, C, ptr(mbuf[o:]), stream), "ffc_bn_reduce")
         tot = 3 * sum(Cs)
         merge_moments(mbuf[:tot].view(-1, 3), group=grp)
     res = {}
-    for (bn, C, slab, nrows, cm), o in zip(batch, offs):
-        use_batch, update = bn_mode(bn)
+    for (bn, C, _, _, _), a, o in zip(batch, recs, offs):
         scale = torch.empty(C, device=device, dtype=torch.float32)
         shift = torch.empty(C, device=device, dtype=torch.float32)
-        momentum = -1.0 if bn.momentum is None else float(bn.momentum)
         with observe("bn_stats"):
-            check(L.ffc_bn_finalize(ptr(mbuf[o:]), C, ptr(bn.weight.detach()) if bn.weight is not None else None,
-                                    ptr(bn.bias.detach()) if bn.bias is not None else None,
-                                    ptr(bn.running_mean) if bn.running_mean is not None else None,
-                                    ptr(bn.running_var) if bn.running_var is not None else None,
-                                    ptr(bn.num_batches_tracked) if bn.num_batches_tracked is not None else None,
-                                    1, int(update), momentum, float(bn.eps), float(cm), ptr(scale), ptr(shift), stream),
-                  "ffc_bn_finalize")
+            bn_finalize(a, mbuf[o:], scale, shift, stream)
         res[id(bn)] = (scale, shift)
     return [res[id(it[0])] if id(it[0]) in res else bn_scale_shift(it[0], it[1], it[2], it[3], it[4], device, stream)
             for it in items]
@@ -327,7 +347,7 @@ class BnFoldDesc:
     scale / shift receive the folded affine (written by the consumer's workgroup 0)"""
 
     def __init__(self, bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device, moments=None):
-        _, update = bn_mode(bn)
+        a = bn_args(bn, C, count_mult, fold=True)
         self.slab = slab
         # SyncBN: the slab's raw moments, reduced and all-reduced over the ranks already ([C][3] fp64,
         # ffc_bn_fold.moments); the consumer finalizes from them
@@ -336,28 +356,13 @@ class BnFoldDesc:
         self.scale = torch.empty(C, device=device, dtype=torch.float32)
         self.shift = torch.empty(C, device=device, dtype=torch.float32)
         self.bn = bn
-        self.struct = _lib.BnFold(
-            ptr(slab), int(nrows), int(C),
-            ptr(bn.weight.detach()) if bn.weight is not None else None,
-            ptr(bn.bias.detach()) if bn.bias is not None else None,
-            ptr(bn.running_mean) if update else None, ptr(bn.running_var) if update else None,
-            ptr(bn.num_batches_tracked) if update else None, int(update),
-            -1.0 if bn.momentum is None else float(bn.momentum), float(bn.eps), float(count_mult),
-            ptr(self.scale), ptr(self.shift), ptr(moments) if moments is not None else None)
+        self.struct = _lib.BnFold(ptr(slab), int(nrows), int(C), *a[1:], ptr(self.scale), ptr(self.shift), ptr(moments))
 
     def materialize(self, stream):
         """(scale, shift) by the separate reduce + finalize launch (consumers without a fold)"""
         if self.moments is not None:   # SyncBN: only the finalize is left (the moments are merged)
-            bn, C = self.bn, self.struct.C
-            _, update = bn_mode(bn)
-            check(lib().ffc_bn_finalize(ptr(self.moments), C, ptr(bn.weight.detach()) if bn.weight is not None else None,
-                                        ptr(bn.bias.detach()) if bn.bias is not None else None,
-                                        ptr(bn.running_mean) if bn.running_mean is not None else None,
-                                        ptr(bn.running_var) if bn.running_var is not None else None,
-                                        ptr(bn.num_batches_tracked) if bn.num_batches_tracked is not None else None,
-                                        1, int(update), -1.0 if bn.momentum is None else float(bn.momentum),
-                                        float(bn.eps), float(self.struct.count_mult), ptr(self.scale),
-                                        ptr(self.shift), stream), "ffc_bn_finalize")
+            bn_finalize(bn_args(self.bn, self.struct.C, self.struct.count_mult), self.moments, self.scale, self.shift,
+                        stream)
             return self.scale, self.shift
         return bn_scale_shift(self.bn, self.struct.C, self.slab, self.struct.nrows, self.struct.count_mult,
                               self.scale.device, stream)
@@ -367,15 +372,9 @@ def _bn_fold_synced(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: fl
     """SyncBN: the slab's raw moments by ffc_bn_reduce, all-reduced over ``grp``
     (RCCL), handed to the consumer kernel as a moments fold -- its workgroups finalize in-kernel, so
     the separate ffc_bn_finalize launch of the N > 1 path goes away"""
-    if bn.num_features != C:
-        raise RuntimeError(f"running_mean should contain {C} elements not {bn.num_features}")
-    L = lib()
-    stream = torch.cuda.current_stream(device).cuda_stream
-    mbuf = torch.empty(3 * C + L.ffc_bn_reduce_ws_doubles(nrows, C), device=device, dtype=torch.float64)
-    from .distributed import merge_moments
+    bn_args(bn, C, count_mult)   # a module of another channel count is refused before anything is launched
     with observe("bn_stats"):
-        check(L.ffc_bn_reduce(ptr(slab), nrows, C, ptr(mbuf), stream), "ffc_bn_reduce")
-        merge_moments(mbuf[:3 * C].view(C, 3), group=grp)
+        mbuf, _ = _bn_reduce_synced(slab, nrows, C, device, torch.cuda.current_stream(device).cuda_stream, grp)
     return BnFoldDesc(bn, C, slab, nrows, count_mult, device, moments=mbuf)
 
 
@@ -390,8 +389,6 @@ def bn_fold(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, dev
         return _bn_fold_synced(bn, C, slab, nrows, count_mult, device, grp) if BN_FOLD_SYNC else None
     if nrows * C > BN_FOLD_MAX:   # every consumer workgroup merges all rows: only small slabs pay
         return None
-    if bn.num_features != C:
-        raise RuntimeError(f"running_mean should contain {C} elements not {bn.num_features}")
     return BnFoldDesc(bn, C, slab, nrows, count_mult, device)
 
 
@@ -441,8 +438,6 @@ def bn_fold_channels(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: f
         return d
     if -(-nrows // lanes) > BN_CHFOLD_LOADS or nrows * max(1, consumers) > BN_CHFOLD_READS:
         return None
-    if bn.num_features != C:
-        raise RuntimeError(f"running_mean should contain {C} elements not {bn.num_features}")
     d = BnFoldDesc(bn, C, slab, nrows, count_mult, device)
     d.channel_only = True
     return d

@@ -21,12 +21,8 @@ constexpr int RED_THREADS = 256;
 #ifndef FFC_BN_SHFL
 #define FFC_BN_SHFL 0
 #endif
-__device__ __forceinline__ double wave_sum_f64(double v) {
-    if constexpr (FFC_BN_SHFL) {
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-        return v;
-    }
+__device__ __forceinline__ double bn_wave_sum_f64(double v) {
+    if constexpr (FFC_BN_SHFL) return ffc::wave_sum_f64(v);
     return ffc::group_sum_f64<64>(v);
 }
 
@@ -57,9 +53,9 @@ __device__ void reduce_channel(const float4* __restrict__ slab, int nrows, int C
         s += en * em;
         q += (double)e.z + en * em * em;
     }
-    n = wave_sum_f64(n);
-    s = wave_sum_f64(s);
-    q = wave_sum_f64(q);
+    n = bn_wave_sum_f64(n);
+    s = bn_wave_sum_f64(s);
+    q = bn_wave_sum_f64(q);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) {
         sh[w][0] = n;
@@ -397,9 +393,9 @@ __global__ __launch_bounds__(64) void bn_merge_kernel(const double* __restrict__
         s += d[1];
         q += d[2];
     }
-    n = wave_sum_f64(n);
-    s = wave_sum_f64(s);
-    q = wave_sum_f64(q);
+    n = bn_wave_sum_f64(n);
+    s = bn_wave_sum_f64(s);
+    q = bn_wave_sum_f64(q);
     if (lane == 0) {
         double* m = moments + 3 * c;
         m[0] = n;

@@ -35,7 +35,9 @@ constexpr int CBN_CHUNK4 = 4 * CBN_THREADS;   // float4 groups per workgroup, pl
 enum { CBN_PLANE = 0, CBN_VEC = 1, CBN_SCALAR = 2 };
 
 // derivative of the activation at pre-activation z (ffc_act_bwd's convention: through the output for
-// ReLU / LeakyReLU / Tanh / Sigmoid, through the input for GELU; here both come from z)
+// ReLU / LeakyReLU / Tanh / Sigmoid, through the input for GELU; here both come from z).  Kept apart from
+// ffc::act_grad on purpose: ffc::act_grad(ffc::apply_act(z), z) is not the same expression (its ReLU /
+// LeakyReLU arms test act(z), these test z itself), and these kernels' arithmetic is pinned as it stands
 __device__ __forceinline__ float cbn_act_grad(float z, int act, float p) {
     switch (act) {
         case FFC_ACT_RELU: return z > 0.0f ? 1.0f : 0.0f;
@@ -176,11 +178,7 @@ struct CbnBwd {
     float p;
 };
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+using ffc::wave_sum_f64;   // the __shfl_xor tree (ffc_internal.h)
 
 // s1 = sum g, s2 = sum g*xh of each plane; G threads per plane (64: one wave, four planes per
 // workgroup; 256: the workgroup).  Every partial sum has a fixed place in a fixed tree: bitwise

@@ -144,6 +144,44 @@ __device__ __forceinline__ float apply_act(float v, int act, float p) {
     }
 }
 
+// derivative of the activation, through its output y for ReLU / LeakyReLU / Tanh / Sigmoid and through
+// its input x for GELU (ffc_act_bwd's convention).  GELU = false: a kernel that keeps only the output and
+// whose entry point refuses GELU (it passes y for x); the arm is compiled out, GELU falls to the default
+template <bool GELU = true>
+__device__ __forceinline__ float act_grad(float y, float x, int act, float p) {
+    switch (act) {
+        case FFC_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
+        case FFC_ACT_LEAKY_RELU: return y > 0.0f ? 1.0f : p;
+        case FFC_ACT_TANH: return 1.0f - y * y;
+        case FFC_ACT_SIGMOID: return y * (1.0f - y);
+        case FFC_ACT_GELU:
+            if constexpr (GELU) {
+                const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
+                const float pdf = 0.39894228040143268f * expf(-0.5f * x * x);
+                return cdf + x * pdf;
+            }
+            return 1.0f;
+        default: return 1.0f;
+    }
+}
+
+// fp64 sum over the wave, in every lane: the xor tree of __shfl_xor (ds_bpermute)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+// fp64 sum over a workgroup of 256 threads, in every thread: wave_sum_f64, then the four waves in a fixed
+// order through red[4] (LDS)
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+    v = wave_sum_f64(v);
+    __syncthreads();   // red may still be read from the previous sum
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
 // Sum over the 32 lanes of each half-wave (lanes l and l^k, k < 32).
 // Sum over each 32-lane half of the wave, in every lane: DPP butterflies inside the 16-lane rows
 // (quad_perm [1,0,3,2], [2,3,0,1], row_half_mirror, row_mirror: VALU, no LDS) and one

@@ -113,17 +113,6 @@ __global__ void pool2_act_kernel(const float* __restrict__ x, long long P, int H
     }
 }
 
-// derivative of the activation through its output (ffc_act_bwd's convention; no GELU here)
-__device__ __forceinline__ float act_grad_out(float y, int act, float p) {
-    switch (act) {
-        case FFC_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
-        case FFC_ACT_LEAKY_RELU: return y > 0.0f ? 1.0f : p;
-        case FFC_ACT_TANH: return 1.0f - y * y;
-        case FFC_ACT_SIGMOID: return y * (1.0f - y);
-        default: return 1.0f;
-    }
-}
-
 __global__ void pool2_act_bwd_kernel(const float* __restrict__ y, const float* __restrict__ dy, long long P, int h,
                                      int w, int act, float ap, float* __restrict__ dx) {
     const int W = 2 * w;
@@ -131,7 +120,7 @@ __global__ void pool2_act_bwd_kernel(const float* __restrict__ y, const float* _
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
         const long long pl = i / per;
         const int r = (int)(i - pl * per), yy = r / w, xx = r - yy * w;
-        const float g = 0.25f * dy[i] * act_grad_out(y[i], act, ap);
+        const float g = 0.25f * dy[i] * ffc::act_grad<false>(y[i], y[i], act, ap);
         float* d = dx + (size_t)pl * 4 * per + (size_t)(2 * yy) * W + 2 * xx;
         d[0] = g;
         d[1] = g;

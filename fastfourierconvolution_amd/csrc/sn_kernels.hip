@@ -94,20 +94,7 @@ __device__ __forceinline__ int sn_col(const SnDev& j, int k) {
     return i * j.stride_i + (k - i * j.R);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-// sum over the workgroup, in every thread: lanes by xor shuffles, the four waves in order
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-    v = wave_sum_f64(v);
-    __syncthreads();   // red may still be read from the previous sum
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
+using ffc::block_sum_f64;   // sum over the workgroup, in every thread (ffc_internal.h)
 
 // ------------------------------------------------------------------ A: partial columns of Wm^T u
 __global__ __launch_bounds__(SN_THREADS) void sn_colsum_kernel(SnTable t) {

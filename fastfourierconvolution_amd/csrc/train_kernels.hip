@@ -25,23 +25,6 @@
 
 namespace {
 
-__device__ __forceinline__ float act_grad_from_out(float y, float x_or_y, int act, float p) {
-    // derivative of the activation expressed through its output y (GELU: through its input)
-    switch (act) {
-        case FFC_ACT_RELU: return y > 0.0f ? 1.0f : 0.0f;
-        case FFC_ACT_LEAKY_RELU: return y > 0.0f ? 1.0f : p;
-        case FFC_ACT_TANH: return 1.0f - y * y;
-        case FFC_ACT_SIGMOID: return y * (1.0f - y);
-        case FFC_ACT_GELU: {
-            const float x = x_or_y;
-            const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));
-            const float pdf = 0.39894228040143268f * expf(-0.5f * x * x);
-            return cdf + x * pdf;
-        }
-        default: return 1.0f;
-    }
-}
-
 // ------------------------------------------------------------------ activation backward
 __global__ void act_bwd_kernel(const float* __restrict__ t, const float* __restrict__ dy, float* __restrict__ dx,
                                long long n, int act, float p) {
@@ -49,7 +32,7 @@ __global__ void act_bwd_kernel(const float* __restrict__ t, const float* __restr
         const float v = t[i];
         float y = v;
         if (act == FFC_ACT_GELU) y = 0.0f;
-        dx[i] = dy[i] * act_grad_from_out(y, v, act, p);
+        dx[i] = dy[i] * ffc::act_grad(y, v, act, p);
     }
 }
 
@@ -112,7 +95,7 @@ __global__ void bn_bwd_partial_kernel(const float* __restrict__ x, const float* 
         const size_t off = ((size_t)b * C + c) * HW + q;
         const float xv = x[off];
         const float z = fmaf(xv, sc, sh);
-        const float g = dy[off] * act_grad_from_out(ffc::apply_act(z, act, p), z, act, p);
+        const float g = dy[off] * ffc::act_grad(ffc::apply_act(z, act, p), z, act, p);
         s1 += g;
         s2 += (double)g * xv;
     }
@@ -184,7 +167,7 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __
         const int c = (int)((i / HW) % C);
         const float xv = x[i];
         const float z = fmaf(xv, scale[c], shift[c]);
-        const float g = dy[i] * act_grad_from_out(ffc::apply_act(z, act, p), z, act, p);
+        const float g = dy[i] * ffc::act_grad(ffc::apply_act(z, act, p), z, act, p);
         dx[i] = fmaf(coef[3 * c], g, fmaf(coef[3 * c + 1], xv, coef[3 * c + 2]));
     }
 }

@@ -131,11 +131,17 @@ def bn_act(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], running_
     return ag.bn_act_impl(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param)
 
 
-@bn_act.register_fake
-def _(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param):
-    C = x.shape[1]
-    stats = x.new_empty((C, 3), dtype=torch.float64) if use_batch else x.new_empty((2, C))
-    return [torch.empty_like(x), x.new_empty(C), x.new_empty(C), stats]
+def _bn_act_fake(up):
+    """the fake of ffc::bn_act and, with ``up``, of ffc::bn_act_up2b (y at twice the height and width)"""
+    def fake(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param):
+        C = x.shape[1]
+        y = x.new_empty((x.shape[0], C, 2 * x.shape[2], 2 * x.shape[3])) if up else torch.empty_like(x)
+        stats = x.new_empty((C, 3), dtype=torch.float64) if use_batch else x.new_empty((2, C))
+        return [y, x.new_empty(C), x.new_empty(C), stats]
+    return fake
+
+
+bn_act.register_fake(_bn_act_fake(False))
 
 
 @torch.library.custom_op("ffc::bn_update_running",
@@ -306,11 +312,7 @@ def bn_act_up2b(x: Tensor, weight: Optional[Tensor], bias: Optional[Tensor], run
     return ag.bn_act_impl(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param, up=True)
 
 
-@bn_act_up2b.register_fake
-def _(x, weight, bias, running_mean, running_var, use_batch, eps, act, act_param):
-    C = x.shape[1]
-    stats = x.new_empty((C, 3), dtype=torch.float64) if use_batch else x.new_empty((2, C))
-    return [x.new_empty((x.shape[0], C, 2 * x.shape[2], 2 * x.shape[3])), x.new_empty(C), x.new_empty(C), stats]
+bn_act_up2b.register_fake(_bn_act_fake(True))
 
 
 def _bn_act_up2b_bwd(ctx, grads):
