@@ -13,7 +13,8 @@ FCondDiscriminator32 (layers/cond/cond_bn.py, fgan_cond_complete.py; set_cond_bn
 transposed-conv baselines the FFC generators are compared against: Generator32 (``Generator`` of
 fgan_complete.py), Generator64 (``Generator`` of fgan64_complete.py) and DCGenerator32 (``Generator`` of
 sngan_complete.py), and the ResNet SNGAN-128 baseline GBlock / DBlock / DBlockOptimized / SNGANGenerator128 /
-SNGANDiscriminator128 (fgan128_complete.py:75-438; resnet.py):
+SNGANDiscriminator128 (fgan128_complete.py:75-438; resnet.py), and the optimizers FusedAdamW / FusedAdam (optim.py:
+torch.optim.AdamW / Adam in one HIP pass, with the reference's linear LR decay on the device):
 
     G = Generator32(z_size=128, mg=4).cuda().eval()      # Generator64 / DCGenerator32 alike
     with torch.no_grad():
@@ -32,6 +33,7 @@ from .layers_misc import GaussianNoise, NoiseInjection, Print, Resizer, debug_pr
 from .models import (CondDiscriminator32, DCGenerator32, Discriminator, Discriminator32, FCondDiscriminator, FCondDiscriminator32,
                      FCondGenerator, FCondGenerator32, FCondGeneratorSTL, FDiscriminator32, FFCDiscriminator,
                      FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32, Generator32, Generator64)
+from .optim import FusedAdam, FusedAdamW
 from .resnet import DBlock, DBlockOptimized, GBlock, SNGANDiscriminator128, SNGANGenerator128
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
@@ -41,4 +43,4 @@ __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose
            "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",
            "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32", "Self_Attn",
            "Generator32", "Generator64", "DCGenerator32", "aw_method", "GBlock", "DBlock", "DBlockOptimized",
-           "SNGANGenerator128", "SNGANDiscriminator128"]
+           "SNGANGenerator128", "SNGANDiscriminator128", "FusedAdamW", "FusedAdam"]

@@ -1460,3 +1460,53 @@ def aw_combine_impl(g_real, g_fake, stats, out):
     with rt.observe("aw_combine", bytes=sum(12.0 * t.numel() for t in g_real)):
         check(rt.lib().ffc_aw_combine(pr, pf, po, numel, n, ptr(stats), AW_JOBS_PER_LAUNCH, _stream(g_real[0])),
               "ffc_aw_combine")
+
+
+# --------------------------------------------------------------------------- fused Adam / AdamW
+OPTIM_JOBS_PER_LAUNCH = 0   # entries per launch of ffc_optim_step: 1..64; 0: the library's 64 (tests vary the split)
+OPTIM_STATE = 4             # int64 words of a state block: [t, s, (lr_eff, step_size), (sqrt_bc2, decay)]
+OPTIM_ADAMW, OPTIM_ADAM = 0, 1
+
+
+def _optim_state(state, what):
+    if state.dtype != torch.int64 or not state.is_cuda or not state.is_contiguous() or not state.numel() or \
+            state.numel() % OPTIM_STATE:
+        raise RuntimeError(f"{what}: state must be a contiguous int64 tensor of {OPTIM_STATE} words per block on the GPU")
+    return state
+
+
+def optim_step_impl(params, grads, exp_avgs, exp_avg_sqs, state, lr, beta1, beta2, eps, weight_decay, decay_steps,
+                    mode):
+    """ffc::optim_step: t <- t + 1 in ``state`` (one block), then torch's single-tensor Adam (mode 1) / AdamW
+    (mode 0) update of every (param, grad, exp_avg, exp_avg_sq) in place, lr scaled on the device by
+    max(0, 1 - s / decay_steps) when decay_steps > 0 (1 + ceil(n / 64) launches); nothing leaves the device"""
+    import ctypes
+    n = len(params)
+    lists = [params, grads, exp_avgs, exp_avg_sqs]
+    if any(len(ts) != n for ts in lists):
+        raise RuntimeError("optim_step: params, grads, exp_avgs and exp_avg_sqs must be lists of the same length")
+    _optim_state(state, "optim_step")
+    if state.numel() != OPTIM_STATE:
+        raise RuntimeError("optim_step: state must be one block")
+    for i in range(n):
+        for ts, what in zip(lists, ("params", "grads", "exp_avgs", "exp_avg_sqs")):
+            t = ts[i]
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+                raise FFCError(f"optim_step: {what}[{i}]: fp32 tensors on the GPU only")
+            if not t.is_contiguous():
+                raise FFCError(f"optim_step: {what}[{i}] must be contiguous")
+            if t.numel() != params[i].numel() or t.device != state.device:
+                raise RuntimeError(f"optim_step: {what}[{i}] does not match params[{i}] (numel) or the state's device")
+    arrays = [(ctypes.c_void_p * n)(*[t.data_ptr() for t in ts]) for ts in lists]
+    numel = (ctypes.c_longlong * n)(*[t.numel() for t in params])
+    with rt.observe("optim_step", bytes=sum(28.0 * t.numel() for t in params)):
+        check(rt.lib().ffc_optim_step(*arrays, numel, n, ptr(state), float(lr), float(beta1), float(beta2), float(eps),
+                                      float(weight_decay), int(decay_steps), int(mode), OPTIM_JOBS_PER_LAUNCH,
+                                      _stream(state)), "ffc_optim_step")
+
+
+def optim_tick_impl(state):
+    """ffc::optim_tick: s <- s + 1 in every block of ``state``: scheduler.step() on the device (one launch)"""
+    _optim_state(state, "optim_tick")
+    with rt.observe("optim_tick", bytes=16.0 * (state.numel() // OPTIM_STATE)):
+        check(rt.lib().ffc_optim_tick(ptr(state), state.numel() // OPTIM_STATE, _stream(state)), "ffc_optim_tick")

@@ -281,6 +281,13 @@ SIGNATURES = [
                                c_int, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     ("ffc_aw_combine", c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                ctypes.POINTER(c_longlong), c_int, c_void_p, c_int, c_void_p]),
+    ("ffc_optim_state_bytes", c_size_t, []),
+    ("ffc_optim_max_jobs", c_int, []),
+    ("ffc_optim_chunk", c_int, []),
+    ("ffc_optim_step", c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                               ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_int, c_void_p, c_double,
+                               c_double, c_double, c_double, c_double, c_longlong, c_int, c_int, c_void_p]),
+    ("ffc_optim_tick", c_int, [c_void_p, c_int, c_void_p]),
     ("ffc_act_up2b", c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float,
                              c_void_p, c_void_p]),
     ("ffc_up2b_adjoint", c_int, [c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p]),

@@ -799,6 +799,37 @@ def _(g_real, g_fake, stats, out):
     return None
 
 
+# ---------------------------------------------------------------- ffc::optim_step / ffc::optim_tick
+# torch.optim's single-tensor Adam / AdamW and LambdaLR(lambda s: 1 - s / T).step() on csrc/optim_kernels.hip, the
+# step and schedule counts in ``state`` on the device; the optimizers are optim.FusedAdamW / FusedAdam
+
+
+@torch.library.custom_op("ffc::optim_step", mutates_args=("params", "exp_avgs", "exp_avg_sqs", "state"))
+def optim_step(params: List[Tensor], grads: List[Tensor], exp_avgs: List[Tensor], exp_avg_sqs: List[Tensor],
+               state: Tensor, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float,
+               decay_steps: int, adam_mode: int) -> None:
+    """state[0] (t) += 1, then the Adam (adam_mode 1) / AdamW (0) update of every entry in place.  (An argument
+    called ``mode`` would collide with a keyword of torch's functionalization of mutating ops.)"""
+    ag.optim_step_impl(params, grads, exp_avgs, exp_avg_sqs, state, lr, beta1, beta2, eps, weight_decay, decay_steps,
+                       adam_mode)
+
+
+@optim_step.register_fake
+def _(params, grads, exp_avgs, exp_avg_sqs, state, lr, beta1, beta2, eps, weight_decay, decay_steps, adam_mode):
+    return None
+
+
+@torch.library.custom_op("ffc::optim_tick", mutates_args=("state",))
+def optim_tick(state: Tensor) -> None:
+    """s += 1 in every 4-word block of ``state``"""
+    ag.optim_tick_impl(state)
+
+
+@optim_tick.register_fake
+def _(state):
+    return None
+
+
 # ---------------------------------------------------------------- ffc::self_attn
 # Self_Attn (layers/attention_layer.py:30-39) after its stacked q / k / v projection, on csrc/attn_kernels.hip
 

@@ -5,7 +5,8 @@ hipGraph capture, bench.py --workload fgan128train) can run the same step the re
 Every convolution, Fourier unit, BatchNorm, activation, NoiseInjection and Linear of G and D runs
 on libffc_amd.so (forward and backward); the hinge losses (a few ops on a (B, 1) tensor), the
 spectral-norm power iteration (torch.nn.utils.spectral_norm's own hook, on the GPU) and the
-optimizer are torch's, as in the reference."""
+optimizer are torch's, as in the reference.  Every step function takes any optimizer: optim.FusedAdamW /
+FusedAdam run the update on libffc_amd.so too, with the reference's LR decay inside a captured iteration."""
 import torch
 import torch.nn.functional as tF
 

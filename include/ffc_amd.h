@@ -853,6 +853,44 @@ int ffc_aw_weights(const float* const* g_real, const float* const* g_fake, const
 int ffc_aw_combine(const float* const* g_real, const float* const* g_fake, float* const* out, const long long* numel,
                    int n, const double* stats, int jobs_per_launch, void* stream);
 
+/* ------------------------------------------------------------------ fused Adam / AdamW step
+ * torch.optim's single-tensor Adam / AdamW (amsgrad = maximize = False) over a list of n (param, grad, exp_avg,
+ * exp_avg_sq) quadruples of contiguous fp32 tensors of numel[i] elements, in place; entries with numel[i] == 0
+ * are skipped (their pointers may be NULL).  The step count and the LR-schedule count live on the device in a
+ * state block of ffc_optim_state_bytes() = 32 bytes, 8-byte aligned, zero before the first step:
+ *   { int64 t;  int64 s;  float lr_eff, step_size, sqrt_bc2, decay; }
+ * ffc_optim_step, in stream order: one thread does t <- t + 1 and derives, in fp64,
+ *   lr_eff    = decay_steps > 0 ? lr * max(0, 1 - s / decay_steps) : lr     (LambdaLR(lambda s: 1 - s / T))
+ *   step_size = lr_eff / (1 - beta1^t)     sqrt_bc2 = sqrt(1 - beta2^t)     decay = 1 - lr_eff * weight_decay
+ * and stores each rounded to fp32 once (decay = 1 in Adam mode).  Then one elementwise fp32 pass
+ *   FFC_OPTIM_ADAMW:  p <- p * decay              FFC_OPTIM_ADAM:  g <- fma((float)weight_decay, p, g)
+ *   m <- lerp(m, g, w1), w1 = (float)(1 - beta1):  fma(w1, g - m, m) when w1 < 0.5, g - (g - m) * (1.0f - w1)
+ *        otherwise (torch's lerp: m = g exactly at beta1 = 0)
+ *   v <- fma((float)(1 - beta2) * g, g, (float)beta2 * v)
+ *   p <- fma(-step_size, m / (sqrt(v) / sqrt_bc2 + (float)eps), p)
+ * with correctly rounded sqrt and divisions and no other contraction.  g = 0 with m = v = 0 leaves exactly
+ * p * decay for eps > 0; lr_eff = 0 leaves p bit-unchanged in AdamW mode.  A workgroup owns ffc_optim_chunk()
+ * = 8192 elements of one tensor; 16-byte accesses when all four tensors of an entry are 16-byte aligned, 4-byte
+ * otherwise; at most ffc_optim_max_jobs() = 64 entries ride in one launch's arguments: 1 + ceil(n' / 64)
+ * launches for n' non-empty entries (jobs_per_launch in 1..64 lowers the 64; anything else: 64).  No atomics,
+ * no workspace; the results are bitwise reproducible and depend neither on jobs_per_launch nor on the alignment.
+ * lr is read by the host call: with decay_steps = 0 a captured graph replays the lr it was captured with.
+ * ffc_optim_tick: s <- s + 1 in each of n_states consecutive state blocks (scheduler.step()).
+ * Nothing synchronises; both calls can be captured into a graph.  FFC_E_INVALID without a launch: n < 0, a NULL
+ * list with n > 0, a NULL pointer of a non-empty entry, numel[i] < 0, tensors of one entry that overlap, a NULL
+ * or misaligned state, beta1 or beta2 outside [0, 1), eps, lr or weight_decay negative or not finite,
+ * decay_steps < 0, a mode other than the two, n_states < 1.  n = 0 is valid and only counts the step.
+ * Pure additions: the ABI version is unchanged. */
+#define FFC_OPTIM_ADAMW 0
+#define FFC_OPTIM_ADAM 1
+size_t ffc_optim_state_bytes(void);
+int ffc_optim_max_jobs(void);
+int ffc_optim_chunk(void);
+int ffc_optim_step(float* const* param, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
+                   const long long* numel, int n, void* state, double lr, double beta1, double beta2, double eps,
+                   double weight_decay, long long decay_steps, int mode, int jobs_per_launch, void* stream);
+int ffc_optim_tick(void* state, int n_states, void* stream);
+
 /* ------------------------------------------------------------------ ResNet SNGAN resampling
  * The resampling steps of GBlock / DBlock and the critic's global sum pooling (fgan128_complete.py:75-438).
  * fp32, dense NCHW planes; no atomics, every sum in one fixed order (bitwise reproducible); any base alignment
