@@ -737,22 +737,27 @@ def linear(lin: nn.Linear, z):
 
 # --------------------------------------------------------------------------- Self_Attn
 def _attn_supported(B, C, H, W, what):
-    """NotImplementedError when the attention kernels refuse the shape; ``what`` leads the message, up to the shape"""
-    if B < 1 or not rt.lib().ffc_attn_supported(C, H, W):
-        raise NotImplementedError(f"{what} {(B, C, H, W)}: the HIP attention kernels take "
-                                  "C % 8 == 0, 8 <= C <= 64, H * W <= 65536")
+    """the entry-point prefix that takes the shape: "ffc_attn" at C <= 64, "ffc_attnw" (the wide kernels) at
+    72 <= C <= 256; NotImplementedError when neither does; ``what`` leads the message, up to the shape"""
+    if B >= 1 and rt.lib().ffc_attn_supported(C, H, W):
+        return "ffc_attn"
+    if B >= 1 and rt.lib().ffc_attnw_supported(C, H, W):
+        return "ffc_attnw"
+    raise NotImplementedError(f"{what} {(B, C, H, W)}: the HIP attention kernels take "
+                              "C % 8 == 0, 8 <= C <= 256, H * W <= 65536")
 
 
 def _attn_dims(x, qkv, what):
-    """(B, C, H, W, d) of a Self_Attn call; NotImplementedError naming the shape when the kernels refuse it"""
+    """(B, C, H, W, d, entry-point prefix) of a Self_Attn call; NotImplementedError naming the shape when the
+    kernels refuse it"""
     if x.dim() != 4:
         raise NotImplementedError(f"{what}: x must be (B, C, H, W), got {tuple(x.shape)}")
     B, C, H, W = x.shape
-    _attn_supported(B, C, H, W, f"{what}: unsupported shape")
+    abi = _attn_supported(B, C, H, W, f"{what}: unsupported shape")
     d = C // 8
     if tuple(qkv.shape) != (B, 2 * d + C, H, W):
         raise RuntimeError(f"{what}: the stacked projection must be {(B, 2 * d + C, H, W)}, got {tuple(qkv.shape)}")
-    return B, C, H, W, d
+    return B, C, H, W, d, abi
 
 
 def _attn_L(L, like, B, N, what):
@@ -779,7 +784,7 @@ def self_attn_impl(x, qkv, gamma, save):
     x = rt.require(x, "x")
     qkv = rt.require(qkv, "qkv")
     gamma = rt.require(gamma, "gamma")
-    B, C, H, W, d = _attn_dims(x, qkv, "Self_Attn")
+    B, C, H, W, d, abi = _attn_dims(x, qkv, "Self_Attn")
     _attn_gamma(gamma, "Self_Attn")
     N = H * W
     y = torch.empty_like(x)
@@ -787,8 +792,9 @@ def self_attn_impl(x, qkv, gamma, save):
     o = torch.empty((B, C, N) if save else (0,), device=x.device, dtype=torch.float32)
     q, k, v = _attn_rows(qkv, d, N)
     with rt.observe("self_attn", flops=2.0 * B * N * N * (d + C)):
-        check(rt.lib().ffc_attn_forward(q, k, v, (2 * d + C) * N, ptr(x), ptr(gamma), ptr(y), ptr(L),
-                                        ptr(o) if save else None, B, C, H, W, _stream(x)), "ffc_attn_forward")
+        check(getattr(rt.lib(), abi + "_forward")(q, k, v, (2 * d + C) * N, ptr(x), ptr(gamma), ptr(y), ptr(L),
+                                                  ptr(o) if save else None, B, C, H, W, _stream(x)),
+              abi + "_forward")
     return [y, L, o]
 
 
@@ -800,7 +806,7 @@ def self_attn_matrix_impl(qkv, L, C):
     if qkv.dim() != 4:
         raise RuntimeError(f"{what}: qkv must be 4-D (B, 2d + C, H, W), got {tuple(qkv.shape)}")
     B, M, H, W = qkv.shape
-    _attn_supported(B, C, H, W, f"{what}: unsupported shape (B, C, H, W) =")
+    abi = _attn_supported(B, C, H, W, f"{what}: unsupported shape (B, C, H, W) =")
     d, N = C // 8, H * W
     if M != 2 * d + C:
         raise RuntimeError(f"{what}: the stacked projection of C = {C} must be {(B, 2 * d + C, H, W)}, got "
@@ -809,8 +815,8 @@ def self_attn_matrix_impl(qkv, L, C):
     P = torch.empty((B, N, N), device=qkv.device, dtype=torch.float32)
     q, k, _ = _attn_rows(qkv, d, N)
     with rt.observe("self_attn_matrix", bytes=4.0 * B * N * N):
-        check(rt.lib().ffc_attn_matrix(q, k, (2 * d + C) * N, ptr(L), ptr(P), B, C, H, W, _stream(qkv)),
-              "ffc_attn_matrix")
+        check(getattr(rt.lib(), abi + "_matrix")(q, k, (2 * d + C) * N, ptr(L), ptr(P), B, C, H, W, _stream(qkv)),
+              abi + "_matrix")
     return P
 
 
@@ -821,7 +827,7 @@ def self_attn_bwd_impl(dy, qkv, o, L, gamma):
     o = rt.require(o, "o")
     L = rt.require(L, "L")
     gamma = rt.require(gamma, "gamma")
-    B, C, H, W, d = _attn_dims(dy, qkv, "Self_Attn backward")
+    B, C, H, W, d, abi = _attn_dims(dy, qkv, "Self_Attn backward")
     N = H * W
     if tuple(o.shape) != (B, C, N):
         raise RuntimeError("Self_Attn backward: the forward ran without save (no attention output kept): o must be "
@@ -830,13 +836,13 @@ def self_attn_bwd_impl(dy, qkv, o, L, gamma):
     _attn_gamma(gamma, "Self_Attn backward")
     dqkv = torch.empty_like(qkv)
     dgamma = torch.empty(1, device=dy.device, dtype=torch.float32)
-    ws = torch.empty(rt.lib().ffc_attn_ws_floats(B, C, H, W), device=dy.device, dtype=torch.float32)
+    ws = torch.empty(getattr(rt.lib(), abi + "_ws_floats")(B, C, H, W), device=dy.device, dtype=torch.float32)
     q, k, v = _attn_rows(qkv, d, N)
     dq, dk, dv = _attn_rows(dqkv, d, N)
     with rt.observe("self_attn_bwd", flops=2.0 * B * N * N * (4 * d + 3 * C)):
-        check(rt.lib().ffc_attn_backward(ptr(dy), q, k, v, (2 * d + C) * N, ptr(o), ptr(L), ptr(gamma), dq, dk, dv,
-                                         (2 * d + C) * N, ptr(dgamma), ptr(ws), B, C, H, W, _stream(dy)),
-              "ffc_attn_backward")
+        check(getattr(rt.lib(), abi + "_backward")(ptr(dy), q, k, v, (2 * d + C) * N, ptr(o), ptr(L), ptr(gamma), dq,
+                                                   dk, dv, (2 * d + C) * N, ptr(dgamma), ptr(ws), B, C, H, W,
+                                                   _stream(dy)), abi + "_backward")
     return [dqkv, dgamma]
 
 

@@ -274,6 +274,15 @@ SIGNATURES = [
     ("ffc_attn_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int,
                                   c_int, c_void_p]),
+    ("ffc_attnw_supported", c_int, [c_int, c_int, c_int]),
+    ("ffc_attnw_ws_floats", c_size_t, [c_int, c_int, c_int, c_int]),
+    ("ffc_attnw_forward", c_int, [c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    ("ffc_attnw_matrix", c_int, [c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                 c_void_p]),
+    ("ffc_attnw_backward", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_longlong, c_void_p, c_void_p, c_int, c_int, c_int,
+                                   c_int, c_void_p]),
     ("ffc_aw_chunk", c_int, []),
     ("ffc_aw_ws_doubles", c_size_t, [ctypes.POINTER(c_longlong), c_int]),
     ("ffc_aw_weights", c_int, [ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), ctypes.POINTER(c_longlong), c_int,

@@ -13,8 +13,9 @@ class Self_Attn(nn.Module):
     gradients flow through ``out`` alone).  Set ``need_attention = False`` to skip it: forward then
     returns (out, None) and nothing of size N x N is allocated.
 
-    x: (B, C, H, W) fp32 on the GPU with C % 8 == 0 and 8 <= C <= 64 (NotImplementedError otherwise);
-    there is no CPU fallback."""
+    x: (B, C, H, W) fp32 on the GPU with C % 8 == 0 and 8 <= C <= 256 (NotImplementedError otherwise);
+    C <= 64 runs the ffc_attn_* entry points, 72 <= C <= 256 the wide ffc_attnw_* ones.
+    There is no CPU fallback."""
 
     need_attention = True
 

@@ -492,3 +492,353 @@ extern "C" int ffc_attn_backward(const float* dy, const float* q, const float* k
     }
     return ffc::launch_status("ffc_attn_backward");
 }
+
+// ==================================================================================== wide channels
+// 72 <= C <= 256 (9 <= d <= 32): the same formulas, tiles and operand orders as above; DESIGN.md §7l.
+// What changes is where the channels go.  S takes up to 16 k-steps (q or k of the wave's own tile in 16
+// registers).  o and dv need P alone, so they are split over channel groups of 64 on a grid axis, each
+// group recomputing S (16 MFMAs against its 32): two accumulator tiles per wave, as at C <= 64.  dq and dk
+// need dS = P (dP - D) and dP sums over every channel, so one wave runs the whole sum (C / 2 k-steps, both
+// operands streamed from memory: 128 registers of its own tile's v or dy spill) and owns a full 32-row dq /
+// dk tile; dv has its own kernel.
+// Nothing is reduced across workgroups except dgamma (attn_dgamma_kernel's fixed order).
+namespace {
+
+constexpr int ATTW_DS = 16;   // k-steps of S: d <= 32
+constexpr int ATTW_GC = 64;   // channels of one group of the forward and of dv
+constexpr int ATTW_MAX_C = 256;
+
+// rows r = 2 s + h of a (d, N) matrix at column n, the B (or A) operand of S's k-step s
+__device__ __forceinline__ void load_rows(const float* __restrict__ p, int d, int N, int n, int h,
+                                          float (&o)[ATTW_DS]) {
+#pragma unroll
+    for (int s = 0; s < ATTW_DS; ++s) {
+        const int r = 2 * s + h;
+        o[s] = r < d ? p[(size_t)min(r, d - 1) * N + n] : 0.0f;
+    }
+}
+
+// the score tile: rows from a (loaded here, column n of a), columns from bf (load_rows of the other side)
+__device__ __forceinline__ floatx16 scores(const float* __restrict__ a, const float (&bf)[ATTW_DS], int d, int N,
+                                           int n, int h) {
+    floatx16 s;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) s[t] = 0.0f;
+#pragma unroll
+    for (int st = 0; st < ATTW_DS; ++st) {
+        if (2 * st < d) {
+            const int r = 2 * st + h;
+            const float av = r < d ? a[(size_t)min(r, d - 1) * N + n] : 0.0f;
+            s = mfma2(av, bf[st], s);
+        }
+    }
+    return s;
+}
+
+// grid (ceil(N / 128), ceil(C / 64), B); blockIdx.y is the channel group, group 0 writes L
+__global__ __launch_bounds__(ATT_THREADS) void attnw_fwd_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ v, long long bs,
+    const float* __restrict__ x, const float* __restrict__ gamma, float* __restrict__ y, float* __restrict__ Lout,
+    float* __restrict__ osave, int C, int d, int N, int vec) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    const int i0 = (blockIdx.x * ATT_WAVES + (threadIdx.x >> 6)) * 32;
+    if (i0 >= N) return;
+    const int c0 = blockIdx.y * ATTW_GC;
+    const size_t b = blockIdx.z;
+    const float* kb = k + b * bs;
+    const float* vb = v + b * bs;
+    float qf[ATTW_DS];
+    load_rows(q + b * bs, d, N, min(i0 + c, N - 1), h, qf);
+    floatx16 o[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) o[cb][t] = 0.0f;
+    float m = -INFINITY, l = 0.0f;
+
+    for (int j0 = 0; j0 < N; j0 += 32) {
+        const bool vt = vec && j0 + 32 <= N;
+        floatx16 s = scores(kb, qf, d, N, min(j0 + c, N - 1), h);   // S^T[j][i]
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {   // padded keys never enter the maximum or the sum
+            if (j0 + rowkey(t, h) >= N) s[t] = -INFINITY;
+            tmax = fmaxf(tmax, s[t]);
+        }
+        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+        const float mn = fmaxf(m, tmax);   // finite: key j0 is real
+        const float alpha = __expf(m - mn);
+        m = mn;
+        float psum = 0.0f;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            s[t] = __expf(s[t] - mn);
+            psum += s[t];
+        }
+        l = fmaf(l, alpha, psum);
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            if (c0 + cb * 32 < C) {   // the last group may hold one block only
+#pragma unroll
+                for (int t = 0; t < 16; ++t) o[cb][t] *= alpha;
+                const int row = c0 + cb * 32 + c;
+                float vv[16];
+                load_keys16(vb + (size_t)min(row, C - 1) * N, j0, h, N, vt, vv);
+#pragma unroll
+                for (int t = 0; t < 16; ++t) o[cb] = mfma2(row < C ? vv[t] : 0.0f, s[t], o[cb]);
+            }
+        }
+    }
+    l += __shfl_xor(l, 32, 64);
+    if (i0 + c >= N) return;   // padded queries are not stored
+    const float inv = 1.0f / l, g = gamma[0];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int row = c0 + cb * 32 + rowkey(t, h);
+            if (row < C) {
+                const size_t idx = (b * C + row) * N + i0 + c;
+                const float ov = o[cb][t] * inv;
+                y[idx] = fmaf(g, ov, x[idx]);
+                if (osave) osave[idx] = ov;
+            }
+        }
+    if (h == 0 && blockIdx.y == 0) Lout[b * N + i0 + c] = m + logf(l);
+}
+
+// grid (ceil(N / 128), B), as attn_matrix_kernel
+__global__ __launch_bounds__(ATT_THREADS) void attnw_matrix_kernel(const float* __restrict__ q,
+                                                                   const float* __restrict__ k, long long bs,
+                                                                   const float* __restrict__ L, float* __restrict__ P,
+                                                                   int d, int N) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    const int i0 = (blockIdx.x * ATT_WAVES + (threadIdx.x >> 6)) * 32;
+    if (i0 >= N) return;
+    const size_t b = blockIdx.y;
+    const float* qb = q + b * bs;
+    float kf[ATTW_DS], Lr[16];
+    load_keys16(L + b * N, i0, h, N, false, Lr);
+    for (int j0 = 0; j0 < N; j0 += 32) {
+        load_rows(k + b * bs, d, N, min(j0 + c, N - 1), h, kf);
+        const floatx16 s = scores(qb, kf, d, N, min(i0 + c, N - 1), h);   // S[i][j]
+        if (j0 + c < N) {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const int i = i0 + rowkey(t, h);
+                if (i < N) P[(b * N + i) * N + j0 + c] = __expf(s[t] - Lr[t]);
+            }
+        }
+    }
+}
+
+// dv[c, j] = gamma sum_i dy[c, i] P[i, j]: key-tile-major, grid (ceil(N / 128), ceil(C / 64), B)
+__global__ __launch_bounds__(ATT_THREADS) void attnw_bwd_v_kernel(
+    const float* __restrict__ dy, const float* __restrict__ q, const float* __restrict__ k, long long bs,
+    const float* __restrict__ L, const float* __restrict__ gamma, float* __restrict__ dv, long long gbs, int C, int d,
+    int N, int vec) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    const int j0 = (blockIdx.x * ATT_WAVES + (threadIdx.x >> 6)) * 32;
+    if (j0 >= N) return;
+    const int c0 = blockIdx.y * ATTW_GC;
+    const size_t b = blockIdx.z;
+    const float* qb = q + b * bs;
+    const float* dyb = dy + b * C * N;
+    const bool jok = j0 + c < N;
+    float kf[ATTW_DS];
+    load_rows(k + b * bs, d, N, min(j0 + c, N - 1), h, kf);
+    floatx16 adv[2];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) adv[cb][t] = 0.0f;
+
+    for (int i0 = 0; i0 < N; i0 += 32) {
+        const bool vt = vec && i0 + 32 <= N;
+        floatx16 s = scores(qb, kf, d, N, min(i0 + c, N - 1), h);   // S[i][j]
+        float Lr[16];
+        load_keys16(L + b * N, i0, h, N, vt, Lr);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) s[t] = (jok && i0 + rowkey(t, h) < N) ? __expf(s[t] - Lr[t]) : 0.0f;
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) {
+            if (c0 + cb * 32 < C) {
+                const int row = c0 + cb * 32 + c;
+                float a[16];
+                load_keys16(dyb + (size_t)min(row, C - 1) * N, i0, h, N, vt, a);
+#pragma unroll
+                for (int t = 0; t < 16; ++t) adv[cb] = mfma2(row < C ? a[t] : 0.0f, s[t], adv[cb]);
+            }
+        }
+    }
+    if (!jok) return;
+    const float g = gamma[0];
+#pragma unroll
+    for (int cb = 0; cb < 2; ++cb)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const int row = c0 + cb * 32 + rowkey(t, h);
+            if (row < C) dv[b * gbs + (size_t)row * N + j0 + c] = g * adv[cb][t];
+        }
+}
+
+// dq (KEYS = false: the wave owns queries n0 .. n0 + 31, walks key tiles, rows of the score tiles are keys)
+// or dk (KEYS = true: owns keys, walks query tiles, rows are queries); grid (ceil(N / 128), B).  own is the
+// matrix of the owned index (q | k), oth the walked one; cown / coth likewise of the channel sum dP (dy | v).
+// With dy in place of do = gamma dy, gamma multiplies the result at the end.
+template <bool KEYS>
+__global__ __launch_bounds__(ATT_THREADS) void attnw_bwd_qk_kernel(
+    const float* __restrict__ own, const float* __restrict__ oth, const float* __restrict__ cown,
+    const float* __restrict__ coth, long long bs, long long cown_bs, long long coth_bs, const float* __restrict__ L,
+    const float* __restrict__ Dn, const float* __restrict__ gamma, float* __restrict__ dout, long long gbs, int C,
+    int d, int N, int vec) {
+    const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
+    const int n0 = (blockIdx.x * ATT_WAVES + (threadIdx.x >> 6)) * 32;
+    if (n0 >= N) return;
+    const size_t b = blockIdx.y;
+    const float* ob = oth + b * bs;
+    const float* cob = coth + b * coth_bs;
+    const float* cwb = cown + b * cown_bs;
+    const int nl = min(n0 + c, N - 1);
+    const bool nok = n0 + c < N;
+    float of[ATTW_DS];
+    load_rows(own + b * bs, d, N, nl, h, of);
+    const float Ln = L[b * N + nl], Dnn = Dn[b * N + nl];   // KEYS = false: the lane's own query
+    floatx16 acc;
+#pragma unroll
+    for (int t = 0; t < 16; ++t) acc[t] = 0.0f;
+
+    for (int m0 = 0; m0 < N; m0 += 32) {
+        const int ml = min(m0 + c, N - 1);
+        const bool vt = vec && m0 + 32 <= N;
+        floatx16 s = scores(ob, of, d, N, ml, h);
+        floatx16 dp;
+#pragma unroll
+        for (int t = 0; t < 16; ++t) dp[t] = 0.0f;
+#pragma unroll 8
+        for (int st = 0; st < C / 2; ++st) {   // dP over every channel (C is even: 2 st + h < C)
+            const size_t cc = 2 * st + h;
+            dp = mfma2(cob[cc * N + ml], cwb[cc * N + nl], dp);
+        }
+        if (KEYS) {
+            float Lr[16], Dr[16];
+            load_keys16(L + b * N, m0, h, N, vt, Lr);
+            load_keys16(Dn + b * N, m0, h, N, vt, Dr);
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const float p = (nok && m0 + rowkey(t, h) < N) ? __expf(s[t] - Lr[t]) : 0.0f;
+                dp[t] = p * (dp[t] - Dr[t]);   // dS / gamma
+            }
+        } else {
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const float p = m0 + rowkey(t, h) < N ? __expf(s[t] - Ln) : 0.0f;
+                dp[t] = p * (dp[t] - Dnn);
+            }
+        }
+        float a[16];   // d(own)[r, n] += sum_m oth[r, m] dS: rows r >= d of the tile are zero
+        load_keys16(ob + (size_t)min(c, d - 1) * N, m0, h, N, vt, a);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) acc = mfma2(c < d ? a[t] : 0.0f, dp[t], acc);
+    }
+    if (!nok) return;
+    const float g = gamma[0];
+#pragma unroll
+    for (int t = 0; t < 16; ++t) {
+        const int r = rowkey(t, h);
+        if (r < d) dout[b * gbs + (size_t)r * N + n0 + c] = g * acc[t];
+    }
+}
+
+const char* attnw_refuse(int B, int C, int H, int W, std::string& msg) {
+    const bool ok = C % 8 == 0 && C >= 72 && C <= ATTW_MAX_C && H >= 1 && W >= 1 &&
+                    (long long)H * W <= ATT_MAX_N && B >= 1 && B <= 65535;
+    if (ok) return nullptr;
+    msg = "unsupported wide Self_Attn shape (B, C, H, W) = (" + std::to_string(B) + ", " + std::to_string(C) + ", " +
+          std::to_string(H) + ", " + std::to_string(W) + "): C % 8 == 0, 72 <= C <= " + std::to_string(ATTW_MAX_C) +
+          ", 1 <= H * W <= " + std::to_string(ATT_MAX_N) + ", 1 <= B <= 65535";
+    return msg.c_str();
+}
+
+#define ATTW_CHECK_SHAPE(name)                                        \
+    do {                                                              \
+        std::string m_;                                               \
+        if (attnw_refuse(B, C, H, W, m_)) {                           \
+            ::ffc::set_error(std::string(name ": ") + m_);            \
+            return FFC_E_INVALID;                                     \
+        }                                                             \
+    } while (0)
+
+void launch_bwd_qk(dim3 grid, hipStream_t st, const float* dy, const float* q, const float* k, const float* v,
+                   long long bs, const float* L, const float* Dn, const float* gamma, float* dq, float* dk,
+                   long long gbs, int C, int d, int N, int vec) {
+    const long long dys = (long long)C * N;
+    hipLaunchKernelGGL((attnw_bwd_qk_kernel<true>), grid, dim3(ATT_THREADS), 0, st, k, q, v, dy, bs, bs, dys, L, Dn,
+                       gamma, dk, gbs, C, d, N, vec);
+    hipLaunchKernelGGL((attnw_bwd_qk_kernel<false>), grid, dim3(ATT_THREADS), 0, st, q, k, dy, v, bs, dys, bs, L, Dn,
+                       gamma, dq, gbs, C, d, N, vec);
+}
+
+}  // namespace
+
+extern "C" int ffc_attnw_supported(int C, int H, int W) {
+    std::string m;
+    return attnw_refuse(1, C, H, W, m) ? 0 : 1;
+}
+
+extern "C" size_t ffc_attnw_ws_floats(int B, int C, int H, int W) {
+    std::string m;
+    if (attnw_refuse(B, C, H, W, m)) return 0;
+    const size_t N = (size_t)H * W;
+    return (size_t)B * N + (size_t)B * ((N + PREP_THREADS - 1) / PREP_THREADS);
+}
+
+extern "C" int ffc_attnw_forward(const float* q, const float* k, const float* v, long long bstride, const float* x,
+                                 const float* gamma, float* y, float* L, float* o, int B, int C, int H, int W,
+                                 void* stream) {
+    ATTW_CHECK_SHAPE("ffc_attnw_forward");
+    FFC_CHECK_ARG(q && k && v && x && gamma && y && L, "ffc_attnw_forward: null pointer");
+    const int N = H * W, d = C / 8;
+    FFC_CHECK_ARG(bstride >= (long long)(2 * d + C) * N, "ffc_attnw_forward: batch stride below (2d + C) N");
+    const int vec = N % 4 == 0 && bstride % 4 == 0 && aligned16(v);
+    const dim3 grid((N + 32 * ATT_WAVES - 1) / (32 * ATT_WAVES), (C + ATTW_GC - 1) / ATTW_GC, B);
+    hipLaunchKernelGGL(attnw_fwd_kernel, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, q, k, v, bstride, x, gamma, y,
+                       L, o, C, d, N, vec);
+    return ffc::launch_status("ffc_attnw_forward");
+}
+
+extern "C" int ffc_attnw_matrix(const float* q, const float* k, long long bstride, const float* L, float* P, int B,
+                                int C, int H, int W, void* stream) {
+    ATTW_CHECK_SHAPE("ffc_attnw_matrix");
+    FFC_CHECK_ARG(q && k && L && P, "ffc_attnw_matrix: null pointer");
+    const int N = H * W, d = C / 8;
+    FFC_CHECK_ARG(bstride >= (long long)d * N, "ffc_attnw_matrix: batch stride below d N");
+    const dim3 grid((N + 32 * ATT_WAVES - 1) / (32 * ATT_WAVES), B);
+    hipLaunchKernelGGL(attnw_matrix_kernel, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, q, k, bstride, L, P, d, N);
+    return ffc::launch_status("ffc_attnw_matrix");
+}
+
+extern "C" int ffc_attnw_backward(const float* dy, const float* q, const float* k, const float* v, long long bstride,
+                                  const float* o, const float* L, const float* gamma, float* dq, float* dk, float* dv,
+                                  long long gbstride, float* dgamma, float* ws, int B, int C, int H, int W,
+                                  void* stream) {
+    ATTW_CHECK_SHAPE("ffc_attnw_backward");
+    FFC_CHECK_ARG(dy && q && k && v && o && L && gamma && dq && dk && dv && dgamma && ws,
+                  "ffc_attnw_backward: null pointer");
+    const int N = H * W, d = C / 8;
+    FFC_CHECK_ARG(bstride >= (long long)(2 * d + C) * N && gbstride >= (long long)(2 * d + C) * N,
+                  "ffc_attnw_backward: batch stride below (2d + C) N");
+    const int vec = N % 4 == 0 && bstride % 4 == 0 && aligned16(q) && aligned16(k) && aligned16(dy) && aligned16(L) &&
+                    aligned16(ws);
+    const int chunks = (N + PREP_THREADS - 1) / PREP_THREADS;
+    float* Dn = ws;
+    float* part = ws + (size_t)B * N;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(attn_bwd_prep_kernel, dim3(chunks, B), dim3(PREP_THREADS), 0, st, dy, o, Dn, part, C, N);
+    hipLaunchKernelGGL(attn_dgamma_kernel, dim3(1), dim3(PREP_THREADS), 0, st, part, B * chunks, dgamma);
+    const int tiles = (N + 32 * ATT_WAVES - 1) / (32 * ATT_WAVES);
+    hipLaunchKernelGGL(attnw_bwd_v_kernel, dim3(tiles, (C + ATTW_GC - 1) / ATTW_GC, B), dim3(ATT_THREADS), 0, st, dy, q,
+                       k, bstride, L, gamma, dv, gbstride, C, d, N, vec);
+    launch_bwd_qk(dim3(tiles, B), st, dy, q, k, v, bstride, L, Dn, gamma, dq, dk, gbstride, C, d, N, vec);
+    return ffc::launch_status("ffc_attnw_backward");
+}

@@ -821,6 +821,22 @@ int ffc_attn_backward(const float* dy, const float* q, const float* k, const flo
                       const float* o, const float* L, const float* gamma, float* dq, float* dk, float* dv,
                       long long gbstride, float* dgamma, float* ws, int B, int C, int H, int W, void* stream);
 
+/* The same layer at C % 8 == 0, 72 <= C <= 256 (9 <= d <= 32; H, W, B as above): the arguments, formulas
+ * and guarantees of the ffc_attn_* counterparts; the ffc_attn_* entry points themselves keep refusing
+ * C > 64.  o and dv are split over channel groups of 64 on a grid axis (each group recomputes S); dq and
+ * dk run the whole channel sum of dP in one wave.  ffc_attnw_backward is five launches (dv has a kernel
+ * of its own).  Anything else returns FFC_E_INVALID ("unsupported ...") before any launch.  Pure
+ * additions: the ABI version is unchanged. */
+int ffc_attnw_supported(int C, int H, int W);
+size_t ffc_attnw_ws_floats(int B, int C, int H, int W);
+int ffc_attnw_forward(const float* q, const float* k, const float* v, long long bstride, const float* x,
+                      const float* gamma, float* y, float* L, float* o, int B, int C, int H, int W, void* stream);
+int ffc_attnw_matrix(const float* q, const float* k, long long bstride, const float* L, float* P, int B, int C,
+                     int H, int W, void* stream);
+int ffc_attnw_backward(const float* dy, const float* q, const float* k, const float* v, long long bstride,
+                       const float* o, const float* L, const float* gamma, float* dq, float* dk, float* dv,
+                       long long gbstride, float* dgamma, float* ws, int B, int C, int H, int W, void* stream);
+
 /* ------------------------------------------------------------------ adaptive-weight critic loss
  * aw_method.aw_loss (layers/aw_loss.py:13-107) after its two backward passes: from the critic's two
  * gradient lists g_real[i], g_fake[i] (n pairs of contiguous fp32 tensors of numel[i] elements; pairs
