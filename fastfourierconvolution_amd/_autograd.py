@@ -101,13 +101,8 @@ def run_conv(cache, key, B, M, segs, weights, inputs, out_shape=None, act=(0, 0.
     dev = inputs[0].device
     # the job's full shape and the plan switches are part of the key (a caller's key alone may leave
     # out the output channels, and one cache serves every module of a structure)
-    key = (key, B, M, tuple(segs), str(dev), rt.plan_knobs())
-    hit = cache.get(key)
-    if hit is None:
-        ex = rt.ConvExec(B, M, list(segs), weights, dev, pw_ok=True)
-        hit = cache[key] = (ex, rt.LaunchPlan([ex], dev))
-    ex, lp = hit
-    ex.ensure_packed(weights)
+    ex, lp = rt.cached_conv(cache, (key, B, M, tuple(segs), str(dev), rt.plan_knobs()), B, M, segs, weights, dev,
+                            pw_ok=True)
     pl = ex.plan
     out = torch.empty(out_shape or (B, pl.M, pl.OH, pl.OW), device=dev, dtype=torch.float32)
     lp.launch([ex.job([(x, None) for x in inputs], out, act[0], act[1], addend, None)], _stream(out),

@@ -352,14 +352,20 @@ class BnFoldDesc:
         # SyncBN: the slab's raw moments, reduced and all-reduced over the ranks already ([C][3] fp64,
         # ffc_bn_fold.moments); the consumer finalizes from them
         self.moments = moments
-        self.channel_only = False   # made by bn_fold_channels: too many rows for a whole-slab fold
+        self.channel_only = False   # make_bn_fold(kind='channels'): too many rows for a whole-slab fold
         self.scale = torch.empty(C, device=device, dtype=torch.float32)
         self.shift = torch.empty(C, device=device, dtype=torch.float32)
         self.bn = bn
         self.struct = _lib.BnFold(ptr(slab), int(nrows), int(C), *a[1:], ptr(self.scale), ptr(self.shift), ptr(moments))
 
+    @property
+    def kind(self) -> str:
+        """the bn_fold_kind this descriptor was made for"""
+        return "moments" if self.moments is not None else "channels" if self.channel_only else "slab"
+
     def materialize(self, stream):
-        """(scale, shift) by the separate reduce + finalize launch (consumers without a fold)"""
+        """(scale, shift) by the separate reduce + finalize launch: for a ready descriptor handed to a
+        Fourier unit whose route does not fold it (FourierUnitSN._run(in_fold=))"""
         if self.moments is not None:   # SyncBN: only the finalize is left (the moments are merged)
             bn_finalize(bn_args(self.bn, self.struct.C, self.struct.count_mult), self.moments, self.scale, self.shift,
                         stream)
@@ -368,28 +374,44 @@ class BnFoldDesc:
                               self.scale.device, stream)
 
 
-def _bn_fold_synced(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device, grp):
-    """SyncBN: the slab's raw moments by ffc_bn_reduce, all-reduced over ``grp``
-    (RCCL), handed to the consumer kernel as a moments fold -- its workgroups finalize in-kernel, so
-    the separate ffc_bn_finalize launch of the N > 1 path goes away"""
+def bn_fold_kind(nrows: int, C: int, use_batch: bool, momentum_none: bool, lanes: Optional[int] = None,
+                 consumers: int = 1) -> Optional[str]:
+    """How a BN over ``nrows`` slab rows of C channels can be finalized inside its consumer kernel, from the
+    switches, the sync group and the row limits alone (no tensor, no launch); None: by its own launch
+    (bn_scale_shift).  Batch statistics only.
+      lanes None: the whole-slab fold (every consumer workgroup merges all rows) -> 'slab', within
+                  BN_FOLD_MAX rows x channels
+      lanes = n:  the per-channel fold (n lanes merge one channel's rows) -> 'channels': BN_CHFOLD on,
+                  momentum not None (the per-channel leaders cannot read num_batches_tracked while another
+                  bumps it), at most BN_CHFOLD_LOADS rows per lane and BN_CHFOLD_READS slab rows read per
+                  channel over its ``consumers`` workgroups (at fgan128's B = 512 every 64^2 C2R plane
+                  workgroup re-read 1024 rows: C2R 798 -> 1046 us per step, r05l)
+    SyncBN -> 'moments' for both, no row gating: the slab's raw moments are reduced and
+    all-reduced first (make_bn_fold) and every consumer reads 3 doubles per channel."""
+    if not (BN_FOLD and use_batch) or (lanes is not None and (not BN_CHFOLD or momentum_none)):
+        return None
+    if _sync_group() is not None:
+        return "moments" if BN_FOLD_SYNC else None
+    if lanes is None:   # every consumer workgroup merges all rows: only small slabs pay
+        return "slab" if nrows * C <= BN_FOLD_MAX else None
+    if -(-nrows // lanes) > BN_CHFOLD_LOADS or nrows * max(1, consumers) > BN_CHFOLD_READS:
+        return None
+    return "channels"
+
+
+def make_bn_fold(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device, kind: str) -> BnFoldDesc:
+    """the BnFoldDesc of a fold bn_fold_kind allowed.  'moments': ffc_bn_reduce and the all-reduce over the
+    sync group (RCCL) run here, and the consumer's workgroups finalize from the merged moments, so the
+    separate ffc_bn_finalize launch of the N > 1 path goes away"""
+    if kind != "moments":
+        d = BnFoldDesc(bn, C, slab, nrows, count_mult, device)
+        d.channel_only = kind == "channels"
+        return d
     bn_args(bn, C, count_mult)   # a module of another channel count is refused before anything is launched
     with observe("bn_stats"):
-        mbuf, _ = _bn_reduce_synced(slab, nrows, C, device, torch.cuda.current_stream(device).cuda_stream, grp)
+        mbuf, _ = _bn_reduce_synced(slab, nrows, C, device, torch.cuda.current_stream(device).cuda_stream,
+                                    _sync_group())
     return BnFoldDesc(bn, C, slab, nrows, count_mult, device, moments=mbuf)
-
-
-def bn_fold(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device):
-    """a BnFoldDesc when ``bn`` can be finalized inside its consumer (batch statistics, one rank),
-    else None (use bn_scale_shift)"""
-    use_batch, _ = bn_mode(bn)
-    if not (BN_FOLD and use_batch and slab is not None):
-        return None
-    grp = _sync_group()
-    if grp is not None:
-        return _bn_fold_synced(bn, C, slab, nrows, count_mult, device, grp) if BN_FOLD_SYNC else None
-    if nrows * C > BN_FOLD_MAX:   # every consumer workgroup merges all rows: only small slabs pay
-        return None
-    return BnFoldDesc(bn, C, slab, nrows, count_mult, device)
 
 
 # SyncBN: reduce + all-reduce the moments, then finalize inside the consumer (ffc_bn_fold.moments)
@@ -417,30 +439,6 @@ FU_SPLIT = _env("FFC_FU_SPLIT", "1", lambda s: s[:1] != "0")
 # 6; off unless FFC_FU_KGROUPS=2, which the library reads too -- measured neutral to slower);
 # FU_KGROUPS = False keeps one workgroup per sample even then
 FU_KGROUPS = True
-
-
-def bn_fold_channels(bn: nn.BatchNorm2d, C: int, slab, nrows: int, count_mult: float, device, lanes: int = 64,
-                     consumers: int = 1):
-    """a BnFoldDesc for a per-channel in-kernel fold (``lanes`` lanes merge one channel's rows), or
-    None: batch statistics on one rank only, momentum not None (the per-channel leaders cannot read
-    num_batches_tracked while another bumps it), at most BN_CHFOLD_LOADS rows per lane, and at most
-    BN_CHFOLD_READS slab rows read per channel over its ``consumers`` workgroups (at fgan128's
-    B = 512 every 64^2 C2R plane workgroup re-read 1024 rows: C2R 798 -> 1046 us per step, r05l)"""
-    use_batch, _ = bn_mode(bn)
-    if not (BN_FOLD and BN_CHFOLD and use_batch and slab is not None) or bn.momentum is None:
-        return None
-    grp = _sync_group()
-    if grp is not None:   # moments: every consumer reads 3 doubles per channel, no row gating
-        if not BN_FOLD_SYNC:
-            return None
-        d = _bn_fold_synced(bn, C, slab, nrows, count_mult, device, grp)
-        d.channel_only = True
-        return d
-    if -(-nrows // lanes) > BN_CHFOLD_LOADS or nrows * max(1, consumers) > BN_CHFOLD_READS:
-        return None
-    d = BnFoldDesc(bn, C, slab, nrows, count_mult, device)
-    d.channel_only = True
-    return d
 
 
 def act_code(mod: nn.Module):
@@ -873,6 +871,114 @@ def conv_route(segs, weights, M, has_addend, has_bn, accept, training=False):
     return route if route in accept else None
 
 
+# ----- the route of a Fourier unit: which kernels run it, and who finalizes which BatchNorm
+class InBn(NamedTuple):
+    """the BatchNorm in front of a Fourier unit (SpectralTransform.bn1) as fu_route looks at it"""
+    nrows: int              # rows of its statistics slab
+    count_mult: float
+    use_batch: bool
+    momentum_none: bool
+    consumers_other: bool = False   # something beside the Fourier unit reads it (run_lfu: the LFU gather)
+    ready: Optional[str] = None     # BnFoldDesc.kind of a descriptor the caller built already (_run(in_fold=))
+
+
+class FuRoute(NamedTuple):
+    """what one FourierUnitSN call launches (fu_route).  Fields a path does not have are None / False."""
+    path: str                   # 'fused' (csrc/fu_kernels.hip, a workgroup per sample) | 'staged' (csrc/fu2d_kernels.hip)
+    stats: bool                 # the unit's own BN runs on batch statistics: a pass 0 fills its slab
+    in_fold: Optional[str]      # the input BN folded into the first kernel, as a make_bn_fold kind: 'slab' |
+    #                             'channels' | 'moments'; None: scale / shift come from their own launch
+    kgroups: int = 1                   # fused pass 0: bin groups per sample
+    spill: bool = False                # pass 0 keeps its mix output Y for the last kernel
+    mix3: bool = False                 # fused: the mix weight's pre-split bf16 pieces (C % 8 == 0)
+    mix_fold: Optional[str] = None     # fused: the unit's BN folded into pass 1: 'split' (per channel) | 'slab'
+    split_lanes: Optional[int] = None  # fused: the lanes per channel the split pass 1's fold was asked for
+    r2c_mix: bool = False              # staged: the R2C inside mix pass 0 (ffc_fu2d_r2c_mix)
+    mix1: Optional[str] = None         # staged: mix pass 1, 'cols' (inverse column FFT fused in) | 'plain'; None: spilled
+    c2r: Optional[str] = None          # staged: 'fold' | 'bn' (BN on load, folded / given) | 'rows' | 'plain'
+    bn_kind: Optional[str] = None      # the make_bn_fold kind behind mix_fold / c2r == 'fold'
+
+
+def fu_route(B, C, H, W, up, mix_precision, use_batch, momentum_none, in_bn: Optional[InBn] = None) -> FuRoute:
+    """The launches of a Fourier unit over (B, C, H, W) planes (``up``: the x2 upsample folded into its loads)
+    whose BN has ``use_batch`` / ``momentum_none``, behind the BatchNorm ``in_bn`` (or none).  Looks at shapes,
+    the switches of this module, the sync group and the library's host-side capability queries; allocates
+    and launches nothing.  Raises NotImplementedError for a plane neither path runs."""
+    L = lib()
+    fused = L.ffc_fu_supported(C, H, W, up) == 1 and not FORCE_FU2D
+    staged_ok = bool(L.ffc_fu2d_supported(C, H, W, up))
+    f16 = mix_precision == "fp16"
+    if f16:
+        if not (staged_ok and C in (16, 32, 64)):
+            raise NotImplementedError(f"fp16 mix: staged FU with C in {{16, 32, 64}} only; got C={C}, {H}x{W}")
+        fused = False
+    if fused and staged_ok and (FU_PATH == "staged" or (FU_PATH == "auto" and B < FU_FUSED_MIN_BATCH)):
+        fused = False
+    if not fused and not staged_ok:
+        raise NotImplementedError(f"Fourier unit supports H,W in {{4,8,16,32}}, square 24x24, or 48x48 as "
+                                  f"the x2-upsampled output of a SpectralTransform (up = 2), with "
+                                  f"16*C*H*(W/2+1) <= 160 KiB (fused), "
+                                  f"or square H=W in {{16,32,64,128}} with 2C <= 128 (staged); "
+                                  f"got C={C}, {H}x{W}")
+    # the fused kernel's planes hold the in-kernel BN fold's scratch (csrc/bn_common.h)
+    fold_ok = 16 * C * H * (W // 2 + 1) >= 8 * 3 * 512 // 4
+    # the input BN as its producer would fold it: over the whole slab, else channel by channel (the staged
+    # r2c's fold); with a second consumer it is finalized by its own launch
+    k1 = None
+    if in_bn is not None and in_bn.ready is not None:
+        k1 = in_bn.ready
+    elif in_bn is not None and in_bn.use_batch and not in_bn.consumers_other:
+        k1 = (bn_fold_kind(in_bn.nrows, C, True, in_bn.momentum_none) or
+              bn_fold_kind(in_bn.nrows, C, True, in_bn.momentum_none, lanes=64))
+    if fused:
+        # pass 0 folds over the whole slab only (a channel fold is not taken: its own launch), and only the
+        # moments fold does without the scratch in the planes; no pass 0 in eval mode, so nothing folds
+        in_fold = k1 if use_batch and (k1 == "moments" or (k1 == "slab" and fold_ok)) else None
+        mix3 = L.ffc_fu_mix3_elems(C) != 0
+        kg, mix_fold, lanes, kind = 1, None, None, None
+        if use_batch:
+            # two bin groups per sample where the library takes them (ffc_fu_kgroups); slab rows = B x groups
+            kg = L.ffc_fu_kgroups(B, C, H, W) if (FU_KGROUPS and FU_SPILL and mix3) else 1
+            rows = L.ffc_fu_slab_rows(B, C, H, W, kg)
+            if FU_SPLIT and FU_SPILL and H == W and H in (8, 16, 32) and C % (64 // H) == 0:
+                # the split pass 1 (one wave per 64 / H channels) folds its 2 * 64 / H channels itself
+                lanes = 64 // (2 * 64 // H)
+                kind = bn_fold_kind(rows, 2 * C, True, momentum_none, lanes=lanes)
+                mix_fold = "split" if kind else None
+            if mix_fold is None and fold_ok:
+                kind = bn_fold_kind(rows, 2 * C, True, momentum_none)
+                mix_fold = "slab" if kind else None
+        return FuRoute("fused", use_batch, in_fold, kgroups=kg, spill=bool(use_batch and FU_SPILL), mix3=mix3,
+                       mix_fold=mix_fold, split_lanes=lanes, bn_kind=kind)
+    # staged: the r2c folds channel by channel, one plane workgroup per (sample, channel): a whole-slab
+    # answer is asked again as a channel fold over B consumers, where the fused path above refuses the
+    # channel fold outright (each answer as the two paths gave it); moments merged over the ranks are
+    # finalized per channel, which needs a momentum
+    if k1 == "moments":
+        in_fold = None if in_bn.momentum_none else "moments"
+    else:
+        in_fold = bn_fold_kind(in_bn.nrows, C, True, in_bn.momentum_none, lanes=64, consumers=B) if k1 else None
+    spill = bool(use_batch and FU2D_SPILL)
+    r2c_mix = bool(spill and FU2D_R2CMIX and not f16 and L.ffc_fu2d_r2c_mix_supported(C, H, W, up))
+    if spill:   # the unit's BN finalized inside the C2R (two channels per plane) where the rows allow
+        kind = bn_fold_kind(L.ffc_fu2d_slab_rows(B, C, H, W), 2 * C, True, momentum_none, lanes=64, consumers=B)
+        return FuRoute("staged", True, in_fold, spill=True, r2c_mix=r2c_mix, c2r="fold" if kind else "bn", bn_kind=kind)
+    cols = bool(FU_COLS and L.ffc_fu2d_cols_supported(C, H, W, up, int(f16)))
+    return FuRoute("staged", use_batch, in_fold, mix1="cols" if cols else "plain", c2r="rows" if cols else "plain")
+
+
+def st_conv1_route(B, Cin, H, W, pool, hid, c) -> str:
+    """SpectralTransform's conv1 over a (B, Cin, H, W) input (``pool``: behind the 2x2 average pool; ``hid``:
+    the SE block's hidden width; c output channels):
+      'prologue'  one fused launch, [pool] -> SE gate -> conv1 -> BN partials, where a sample fits in LDS
+      'pw_gate'   SE gate, then conv1 with the gate folded into the per-sample weights (csrc/st_pw.hip)
+      'gemm'      SE gate, then the implicit-GEMM kernels (the pooled input, or channels over st_pw's LDS)"""
+    L = lib()
+    if ST_PATH != "pw" and L.ffc_st_prologue_lds_bytes(Cin, H, W, int(pool), hid, c) > 0:
+        return "prologue"
+    return "pw_gate" if not pool and L.ffc_pw_gate_lds_bytes(Cin, c) > 0 else "gemm"
+
+
 def smallm_forward(route, segs, weights, xs, M, B, act, stream, packs=None, pack_slot=None, tfs=None):
     """launch the direct kernel of a 'convT' / 'full' / 'conv3' / 'convT3' job (conv_route) -> out.
     packs, pack_slot: the PackCache (and its slot, see there) for the convT kernel's packed weights;
@@ -1203,6 +1309,17 @@ class LaunchPlan:
                 arr = (_lib.ConvJob * len(jobs))(*jobs)
                 check(L.ffc_conv_forward(arr, len(jobs), self.tiles.data_ptr(), self.ntiles, self.cfg, stream),
                       "ffc_conv_forward")
+
+
+def cached_conv(cache, key, B, M, segs, weights, device, pw_ok=False):
+    """-> (ConvExec, LaunchPlan) of a one-job launch kept in ``cache`` under ``key`` (made on a miss), its
+    weights re-packed where they changed"""
+    hit = cache.get(key)
+    if hit is None:
+        ex = ConvExec(B, M, list(segs), weights, device, pw_ok=pw_ok)
+        hit = cache[key] = (ex, LaunchPlan([ex], device))
+    hit[0].ensure_packed(weights)
+    return hit
 
 
 def sn_refresh(mod):

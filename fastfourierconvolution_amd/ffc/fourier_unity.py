@@ -63,88 +63,6 @@ class FourierUnitSN(nn.Module):
             return w3
         return self._packs.get("mix3", [rt.require(w.detach(), "conv_layer.weight")], build)
 
-    @staticmethod
-    def _fold_ok(C, H, W):
-        """the fused kernel's planes hold the in-kernel BN fold's scratch (csrc/bn_common.h)"""
-        return 16 * C * H * (W // 2 + 1) >= 8 * 3 * 512 // 4
-
-    def _run(self, t, up=1, in_scale=None, in_shift=None, in_relu=False, residual=False, in_fold=None):
-        """fused FU over s = transform(t) (see include/ffc_amd.h ffc_fu_forward_ex).  in_fold: the
-        input BN (SpectralTransform.bn1) as an rt.BnFoldDesc, finalized inside pass 0."""
-        B, C, th, tw = t.shape
-        H, W = th * up, tw * up
-        self._check(C)
-        L = rt.lib()
-        fused = L.ffc_fu_supported(C, H, W, up) == 1 and not rt.FORCE_FU2D
-        staged_ok = L.ffc_fu2d_supported(C, H, W, up)
-        if self.mix_precision == "fp16":
-            if not (staged_ok and C in (16, 32, 64)):
-                raise NotImplementedError(f"fp16 mix: staged FU with C in {{16, 32, 64}} only; got C={C}, {H}x{W}")
-            fused = False
-        if fused and staged_ok and (rt.FU_PATH == "staged" or (rt.FU_PATH == "auto" and B < rt.FU_FUSED_MIN_BATCH)):
-            fused = False
-        if in_fold is not None and fused and in_fold.moments is None and (in_fold.channel_only or
-                                                                          not self._fold_ok(C, H, W)):
-            in_scale, in_shift = in_fold.materialize(rt.stream_of(t))
-            in_fold = None
-        if not fused:
-            if L.ffc_fu2d_supported(C, H, W, up):
-                return self._run2d(t, up, in_scale, in_shift, in_relu, residual, in_fold)
-            raise NotImplementedError(f"Fourier unit supports H,W in {{4,8,16,32}}, square 24x24, or 48x48 as "
-                                      f"the x2-upsampled output of a SpectralTransform (up = 2), with "
-                                      f"16*C*H*(W/2+1) <= 160 KiB (fused), "
-                                      f"or square H=W in {{16,32,64,128}} with 2C <= 128 (staged); "
-                                      f"got C={C}, {H}x{W}")
-        dev = t.device
-        stream = rt.stream_of(t)
-        mixT = self._packed_mix(dev, stream)
-        mix3 = self._packed_mix3(mixT, dev, stream)
-        use_batch, _ = rt.bn_mode(self.bn)
-        n_r = float(B * C * H * W)              # SURVEY.md §8d: fused FU moves 4*N_r per read/write
-        n_y = float(B * 2 * C * H * (W // 2 + 1))
-        sc = sh = mix_fold = yspill = None
-        kg = 1
-        if use_batch:
-            # pass 0 over two bin groups per sample where the library takes them (ffc_fu_kgroups: half
-            # the spectrum's columns per workgroup, two workgroups per CU); slab rows = B x groups
-            kg = L.ffc_fu_kgroups(B, C, H, W) if (rt.FU_KGROUPS and rt.FU_SPILL and mix3 is not None) else 1
-            rows = L.ffc_fu_slab_rows(B, C, H, W, kg)
-            slab = torch.empty((rows, 2 * C, 4), device=dev, dtype=torch.float32)
-            # pass 0 keeps its mix output Y for pass 1 (no second row R2C + column FFT + mix)
-            yspill = torch.empty(int(n_y), device=dev, dtype=torch.float32) if rt.FU_SPILL else None
-            # bytes: SURVEY.md §8d's algorithmic basis (fused train FU = 12*N_r: x read in each pass,
-            # out written once), never more than the kernel moves (t is read at the pre-upsample size);
-            # moved: what this kernel pair actually streams (including the Y spill written and read back)
-            mv0 = 4.0 * t.numel() + (4.0 * n_y if rt.FU_SPILL else 0.0)
-            with rt.observe("fu_pass0", bytes=min(4.0 * n_r, mv0), moved=mv0):
-                check(L.ffc_fu_forward_ex4(ptr(t), B, C, H, W, up, None if in_fold else ptr(in_scale),
-                                           None if in_fold else ptr(in_shift), int(in_relu), ptr(mixT), ptr(mix3), 0,
-                                           ptr(slab), None, None, 0, None,
-                                           ctypes.byref(in_fold.struct) if in_fold else None, None, ptr(yspill),
-                                           kg, stream), "ffc_fu_forward(pass 0)")
-            if in_fold is not None:          # pass 0's workgroup 0 wrote the folded bn1 affine
-                in_scale, in_shift = in_fold.scale, in_fold.shift
-            mix_fold = None
-            if rt.FU_SPLIT and yspill is not None and H == W and H in (8, 16, 32) and C % (64 // H) == 0:
-                # the split pass 1 (one wave per 64 / H channels) folds its 2 * 64 / H channels itself
-                mix_fold = rt.bn_fold_channels(self.bn, 2 * C, slab, rows, 1.0, dev, lanes=64 // (2 * 64 // H))
-            if mix_fold is None and self._fold_ok(C, H, W):
-                mix_fold = rt.bn_fold(self.bn, 2 * C, slab, rows, 1.0, dev)
-            if mix_fold is None:
-                sc, sh = rt.bn_scale_shift(self.bn, 2 * C, slab, rows, 1.0, dev, stream)
-        else:
-            if in_fold is not None:
-                in_scale, in_shift = in_fold.materialize(stream)
-            sc, sh = rt.bn_scale_shift(self.bn, 2 * C, None, 0, 1.0, dev, stream)
-        out = torch.empty((B, C, H, W), device=dev, dtype=torch.float32)
-        mv1 = (4.0 * n_y if yspill is not None else 4.0 * t.numel()) + 4.0 * t.numel() * bool(residual) + 4.0 * n_r
-        with rt.observe("fu_pass1", bytes=min(8.0 * n_r, mv1), moved=mv1):
-            check(L.ffc_fu_forward_ex4(ptr(t), B, C, H, W, up, ptr(in_scale), ptr(in_shift), int(in_relu), ptr(mixT),
-                                       ptr(mix3), 1, None, ptr(sc), ptr(sh), int(residual), ptr(out), None,
-                                       ctypes.byref(mix_fold.struct) if mix_fold else None, ptr(yspill), kg, stream),
-                  "ffc_fu_forward(pass 1)")
-        return out
-
     def _packed_mix16(self, device, stream):
         w = rt.require(self.conv_layer.weight.detach(), "conv_layer.weight")
 
@@ -155,105 +73,129 @@ class FourierUnitSN(nn.Module):
             return mix16
         return self._packs.get("mix16", [w], build)
 
-    def _run2d(self, t, up, in_scale, in_shift, in_relu, residual, in_fold=None):
-        """large-plane FU: r2c -> mix (pass 0 stats, pass 1 BN/ReLU) -> c2r (include/ffc_amd.h ffc_fu2d_*).
-        in_fold: the input BN as an rt.BnFoldDesc -- finalized inside the r2c, one channel per plane
-        workgroup, when that fold applies (rt.bn_fold_channels), else by its own launch"""
+    def route(self, B, C, H, W, up, in_bn=None):
+        """rt.fu_route of this unit over (B, C, H, W) planes behind the BatchNorm ``in_bn`` (an rt.InBn)"""
+        self._check(C)
+        return rt.fu_route(B, C, H, W, up, self.mix_precision, rt.bn_mode(self.bn)[0], self.bn.momentum is None, in_bn)
+
+    def _run(self, t, up=1, in_scale=None, in_shift=None, in_relu=False, residual=False, in_fold=None):
+        """the Fourier unit over s = transform(t) (include/ffc_amd.h ffc_fu_forward_ex4 / ffc_fu2d_*).  in_fold:
+        the input BN as a ready rt.BnFoldDesc, finalized inside the first kernel where the route folds it"""
         B, C, h, w = t.shape
+        in_bn = None
         if in_fold is not None:
-            if in_fold.moments is not None:   # SyncBN: already merged over the ranks; per-channel needs momentum
-                chf = in_fold if in_fold.bn.momentum is not None else None
-            else:
-                chf = rt.bn_fold_channels(in_fold.bn, C, in_fold.slab, in_fold.struct.nrows,
-                                          in_fold.struct.count_mult, t.device, consumers=B)
-            if chf is None:
-                in_scale, in_shift = in_fold.materialize(rt.stream_of(t))
-                in_fold = None
-            else:
-                in_fold = chf
+            in_bn = rt.InBn(in_fold.struct.nrows, in_fold.struct.count_mult, True, in_fold.bn.momentum is None,
+                            ready=in_fold.kind)
+        r = self.route(B, C, h * up, w * up, up, in_bn)
+        if in_fold is not None and r.in_fold is None:
+            in_scale, in_shift = in_fold.materialize(rt.stream_of(t))
+            in_fold = None
+        elif in_fold is not None and r.in_fold != in_fold.kind:   # a whole-slab descriptor, folded by channel
+            in_fold = rt.make_bn_fold(in_fold.bn, C, in_fold.slab, in_fold.struct.nrows, in_fold.struct.count_mult,
+                                      t.device, r.in_fold)
+        return self._launch(r, t, up, in_scale, in_shift, in_relu, residual, in_fold)
+
+    def _launch(self, r, t, up, in_scale, in_shift, in_relu, residual, in_fold):
+        """the launches of route ``r`` (an rt.FuRoute).  in_fold: the rt.BnFoldDesc of r.in_fold, which the first
+        kernel finalizes into in_fold.scale / in_fold.shift; else the input BN arrives as in_scale / in_shift"""
+        B, C, h, w = t.shape
         H, W = h * up, w * up
-        L = rt.lib()
-        dev = t.device
-        stream = rt.stream_of(t)
+        L, dev, stream = rt.lib(), t.device, rt.stream_of(t)
+        fold_arg = ctypes.byref(in_fold.struct) if in_fold else None
+        n_r, n_c = float(B * C * H * W), float(B * C * H * (W // 2 + 1))   # SURVEY.md §8d: real / complex elements
+        n_t = 4.0 * t.numel()                                             # bytes of t (the pre-upsample size)
+        sc = sh = slab = rows = None
+        if r.path == "fused":
+            mixT = self._packed_mix(dev, stream)
+            mix3 = self._packed_mix3(mixT, dev, stream)
+            mix_fold = yspill = None
+            if r.stats:
+                rows = L.ffc_fu_slab_rows(B, C, H, W, r.kgroups)
+                slab = torch.empty((rows, 2 * C, 4), device=dev, dtype=torch.float32)
+                # pass 0 keeps its mix output Y for pass 1 (no second row R2C + column FFT + mix)
+                yspill = torch.empty(int(2 * n_c), device=dev, dtype=torch.float32) if r.spill else None
+                # bytes: SURVEY.md §8d's algorithmic basis (fused train FU = 12*N_r: x read in each pass,
+                # out written once), never more than the kernel moves (t is read at the pre-upsample size);
+                # moved: what this kernel pair actually streams (including the Y spill written and read back)
+                mv0 = n_t + (8.0 * n_c if r.spill else 0.0)
+                with rt.observe("fu_pass0", bytes=min(4.0 * n_r, mv0), moved=mv0):
+                    check(L.ffc_fu_forward_ex4(ptr(t), B, C, H, W, up, None if in_fold else ptr(in_scale),
+                                               None if in_fold else ptr(in_shift), int(in_relu), ptr(mixT), ptr(mix3), 0,
+                                               ptr(slab), None, None, 0, None, fold_arg, None, ptr(yspill), r.kgroups,
+                                               stream), "ffc_fu_forward(pass 0)")
+                if in_fold is not None:          # pass 0's workgroup 0 wrote the folded bn1 affine
+                    in_scale, in_shift = in_fold.scale, in_fold.shift
+                if r.mix_fold:
+                    mix_fold = rt.make_bn_fold(self.bn, 2 * C, slab, rows, 1.0, dev, r.bn_kind)
+            if mix_fold is None:
+                sc, sh = rt.bn_scale_shift(self.bn, 2 * C, slab, rows or 0, 1.0, dev, stream)
+            out = torch.empty((B, C, H, W), device=dev, dtype=torch.float32)
+            mv1 = (8.0 * n_c if yspill is not None else n_t) + n_t * bool(residual) + 4.0 * n_r
+            with rt.observe("fu_pass1", bytes=min(8.0 * n_r, mv1), moved=mv1):
+                check(L.ffc_fu_forward_ex4(ptr(t), B, C, H, W, up, ptr(in_scale), ptr(in_shift), int(in_relu),
+                                           ptr(mixT), ptr(mix3), 1, None, ptr(sc), ptr(sh), int(residual), ptr(out), None,
+                                           ctypes.byref(mix_fold.struct) if mix_fold else None, ptr(yspill), r.kgroups,
+                                           stream), "ffc_fu_forward(pass 1)")
+            return out
+        # staged: r2c -> mix (pass 0 stats, pass 1 BN/ReLU) -> c2r
         f16 = self.mix_precision == "fp16"
         mixT = self._packed_mix16(dev, stream) if f16 else self._packed_mix(dev, stream)
         mixfn = L.ffc_fu2d_mix_f16 if f16 else L.ffc_fu2d_mix
-        use_batch, _ = rt.bn_mode(self.bn)
         nT = B * C * h * (w // 2 + 1)           # complex bins of T
-        nY = B * C * H * (W // 2 + 1)           # complex bins of Y
         mix_flops = 2.0 * (2 * C) ** 2 * (B * H * (W // 2 + 1))   # (2C x 2C) GEMM over every bin
-        n_r, n_c = float(B * C * H * W), float(B * C * H * (W // 2 + 1))   # SURVEY.md §8d, full resolution
-        # SURVEY.md §8d's R2C bytes, capped at what the kernel moves: with the upsample folded in it
-        # reads t (N_r / 4) and writes T (N_c / 4), and counting the full-resolution bytes would credit
-        # bytes never transferred
-        mvr = 4.0 * t.numel() + 8.0 * nT
         out = torch.empty((B, C, H, W), device=dev, dtype=torch.float32)
-        c2r_moved = 8.0 * nY + 4.0 * out.numel() + (4.0 * t.numel() if residual else 0.0)
-        c2r_bytes = min(8.0 * n_c + 4.0 * n_r, c2r_moved)                   # SURVEY.md §8d C2R pass
-        fused_r2c = (use_batch and rt.FU2D_SPILL and rt.FU2D_R2CMIX and not f16 and
-                     L.ffc_fu2d_r2c_mix_supported(C, H, W, up))
-        T = None
-        if not fused_r2c:
+        T = Y = cfold = None
+        if not r.r2c_mix:
+            # SURVEY.md §8d's R2C bytes, capped at what the kernel moves: with the upsample folded in it
+            # reads t (N_r / 4) and writes T (N_c / 4), and counting the full-resolution bytes would credit
+            # bytes never transferred
+            mvr = n_t + 8.0 * nT
             T = torch.empty((B, C, h, w // 2 + 1, 2), device=dev, dtype=torch.float32)
             with rt.observe("fu2d_r2c", bytes=min(4.0 * n_r + 8.0 * n_c, mvr), moved=mvr):
-                check(L.ffc_fu2d_r2c_ex(ptr(t), B, C, h, w, ptr(in_scale), ptr(in_shift), int(in_relu),
-                                        ctypes.byref(in_fold.struct) if in_fold else None, ptr(T), stream),
-                      "ffc_fu2d_r2c")
-        if use_batch:
+                check(L.ffc_fu2d_r2c_ex(ptr(t), B, C, h, w, ptr(in_scale), ptr(in_shift), int(in_relu), fold_arg, ptr(T),
+                                        stream), "ffc_fu2d_r2c")
+        if r.stats:
             rows = L.ffc_fu2d_slab_rows(B, C, H, W)
             slab = torch.empty((rows, 2 * C, 4), device=dev, dtype=torch.float32)
             # spill: pass 0 stores the raw Y and the C2R applies BN + ReLU on load (one mix instead of
             # two, and the statistics are taken from exactly the values they normalise)
-            Y = torch.empty((B, C, H, W // 2 + 1, 2), device=dev, dtype=torch.float32) if rt.FU2D_SPILL else None
-            if fused_r2c:
+            Y = torch.empty((B, C, H, W // 2 + 1, 2), device=dev, dtype=torch.float32) if r.spill else None
+            if r.r2c_mix:
                 # the R2C inside mix pass 0 (small t planes: every bin-range workgroup recomputes its
                 # sample's T in LDS); labelled as the R2C stage, bytes = t in + the spilled Y out
-                mv = 4.0 * t.numel() + 8.0 * nY
+                mv = n_t + 8.0 * n_c
                 with rt.observe("fu2d_r2c", flops=mix_flops, bytes=min(4.0 * n_r + 8.0 * n_c, mv), moved=mv):
                     check(L.ffc_fu2d_r2c_mix(ptr(t), B, C, H, W, up, ptr(in_scale), ptr(in_shift), int(in_relu),
-                                             ctypes.byref(in_fold.struct) if in_fold else None, ptr(mixT),
-                                             ptr(slab), ptr(Y), stream), "ffc_fu2d_r2c_mix")
+                                             fold_arg, ptr(mixT), ptr(slab), ptr(Y), stream), "ffc_fu2d_r2c_mix")
             else:
-                with rt.observe("fu2d_mix0", flops=mix_flops, bytes=8.0 * nT + (8.0 * nY if Y is not None else 0.0)):
+                with rt.observe("fu2d_mix0", flops=mix_flops, bytes=8.0 * nT + (8.0 * n_c if r.spill else 0.0)):
                     check(mixfn(ptr(T), B, C, H, W, up, ptr(mixT), 0, ptr(slab), None, None, ptr(Y), stream),
                           "ffc_fu2d_mix(pass 0)")
-            if in_fold is not None:   # the r2c's (or r2c_mix's) leader workgroups wrote the folded bn1 affine
-                in_scale, in_shift = in_fold.scale, in_fold.shift
-            cfold = rt.bn_fold_channels(self.bn, 2 * C, slab, rows, 1.0, dev, consumers=B) if Y is not None else None
-            if cfold is not None:   # the FU's BN finalized inside the C2R (two channels per plane)
-                with rt.observe("fu2d_c2r", bytes=c2r_bytes, moved=c2r_moved):
-                    check(L.ffc_fu2d_c2r_fold(ptr(Y), B, C, H, W, ptr(t), up, ptr(in_scale), ptr(in_shift),
-                                              int(in_relu), int(residual), ctypes.byref(cfold.struct), ptr(out),
-                                              stream), "ffc_fu2d_c2r_fold")
-                return out
-            sc, sh = rt.bn_scale_shift(self.bn, 2 * C, slab, rows, 1.0, dev, stream)
-            if Y is not None:
-                with rt.observe("fu2d_c2r", bytes=c2r_bytes, moved=c2r_moved):
-                    check(L.ffc_fu2d_c2r_bn(ptr(Y), B, C, H, W, ptr(t), up, ptr(in_scale), ptr(in_shift),
-                                            int(in_relu), int(residual), ptr(sc), ptr(sh), ptr(out), stream),
-                          "ffc_fu2d_c2r_bn")
-                return out
-        else:
-            sc, sh = rt.bn_scale_shift(self.bn, 2 * C, None, 0, 1.0, dev, stream)
-        if in_fold is not None and not use_batch:
+        if in_fold is not None:   # the r2c's (or r2c_mix's) leader workgroups wrote the folded bn1 affine
             in_scale, in_shift = in_fold.scale, in_fold.shift
-        if rt.FU_COLS and L.ffc_fu2d_cols_supported(C, H, W, up, int(f16)):
+        if r.c2r == "fold":   # the FU's BN finalized inside the C2R (two channels per plane)
+            cfold = rt.make_bn_fold(self.bn, 2 * C, slab, rows, 1.0, dev, r.bn_kind)
+        else:
+            sc, sh = rt.bn_scale_shift(self.bn, 2 * C, slab, rows or 0, 1.0, dev, stream)
+        if r.mix1 == "cols":
             # pass 1 with the inverse column FFT fused in (column-major Yc), then rows-only C2R
-            Yc = torch.empty((B, C, W // 2 + 1, H, 2), device=dev, dtype=torch.float32)
-            with rt.observe("fu2d_mix1", flops=mix_flops, bytes=8.0 * nT + 8.0 * nY):
-                check(L.ffc_fu2d_mix_cols(ptr(T), B, C, H, W, up, ptr(mixT), int(f16), ptr(sc), ptr(sh), ptr(Yc),
+            Y = torch.empty((B, C, W // 2 + 1, H, 2), device=dev, dtype=torch.float32)
+            with rt.observe("fu2d_mix1", flops=mix_flops, bytes=8.0 * nT + 8.0 * n_c):
+                check(L.ffc_fu2d_mix_cols(ptr(T), B, C, H, W, up, ptr(mixT), int(f16), ptr(sc), ptr(sh), ptr(Y),
                                           stream), "ffc_fu2d_mix_cols")
-            with rt.observe("fu2d_c2r", bytes=c2r_bytes, moved=c2r_moved):
-                check(L.ffc_fu2d_c2r_rows(ptr(Yc), B, C, H, W, ptr(t), up, ptr(in_scale), ptr(in_shift),
-                                          int(in_relu), int(residual), ptr(out), stream), "ffc_fu2d_c2r_rows")
-            return out
-        Y = torch.empty((B, C, H, W // 2 + 1, 2), device=dev, dtype=torch.float32)
-        with rt.observe("fu2d_mix1", flops=mix_flops, bytes=8.0 * nT + 8.0 * nY):
-            check(mixfn(ptr(T), B, C, H, W, up, ptr(mixT), 1, None, ptr(sc), ptr(sh), ptr(Y), stream),
-                  "ffc_fu2d_mix(pass 1)")
-        with rt.observe("fu2d_c2r", bytes=c2r_bytes, moved=c2r_moved):
-            check(L.ffc_fu2d_c2r(ptr(Y), B, C, H, W, ptr(t), up, ptr(in_scale), ptr(in_shift), int(in_relu),
-                                 int(residual), ptr(out), stream), "ffc_fu2d_c2r")
+        elif r.mix1 == "plain":
+            Y = torch.empty((B, C, H, W // 2 + 1, 2), device=dev, dtype=torch.float32)
+            with rt.observe("fu2d_mix1", flops=mix_flops, bytes=8.0 * nT + 8.0 * n_c):
+                check(mixfn(ptr(T), B, C, H, W, up, ptr(mixT), 1, None, ptr(sc), ptr(sh), ptr(Y), stream),
+                      "ffc_fu2d_mix(pass 1)")
+        # the C2R of r.c2r: the whole-plane kernel with the BN on load (folded here, or given) or plain, or
+        # the rows-only kernel behind mix_cols
+        name = "ffc_fu2d_c2r" + {"fold": "_fold", "bn": "_bn", "rows": "_rows", "plain": ""}[r.c2r]
+        tail = (ctypes.byref(cfold.struct),) if r.c2r == "fold" else (ptr(sc), ptr(sh)) if r.c2r == "bn" else ()
+        c2r_moved = 8.0 * n_c + 4.0 * out.numel() + (n_t if residual else 0.0)
+        with rt.observe("fu2d_c2r", bytes=min(8.0 * n_c + 4.0 * n_r, c2r_moved), moved=c2r_moved):   # §8d C2R pass
+            check(getattr(L, name)(ptr(Y), B, C, H, W, ptr(t), up, ptr(in_scale), ptr(in_shift), int(in_relu),
+                                   int(residual), *tail, ptr(out), stream), name)
         return out
 
     def forward(self, x, y=None):

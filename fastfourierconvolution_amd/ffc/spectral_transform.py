@@ -182,7 +182,8 @@ class SpectralTransform(nn.Module):
         L = rt.lib()
         hid = self.se_block.fc[0].out_features
         t = torch.empty((B, c, h2, w2), device=dev, dtype=torch.float32)
-        if rt.ST_PATH != "pw" and L.ffc_st_prologue_lds_bytes(Cin, H, W, int(pool), hid, c) > 0:
+        conv1 = rt.st_conv1_route(B, Cin, H, W, pool, hid, c)
+        if conv1 == "prologue":
             # one fused launch: [pool] -> SE gate -> conv1 -> per-sample BN1 partials
             se1 = rt.require(self.se_block.fc[0].weight.detach(), "se.fc.0.weight") if hid > 0 else None
             se2 = rt.require(self.se_block.fc[2].weight.detach(), "se.fc.2.weight") if hid > 0 else None
@@ -195,7 +196,7 @@ class SpectralTransform(nn.Module):
             with rt.observe("st_prologue", flops=2.0 * B * c * Cin * h2 * w2):
                 check(L.ffc_st_prologue_ex3(ptr(x), B, Cin, H, W, int(pool), ptr(se1), ptr(se2), hid, ptr(wc),
                                             ptr(wc3), c, split, ptr(t), ptr(slab), None, stream), "ffc_st_prologue")
-        elif not pool and L.ffc_pw_gate_lds_bytes(Cin, c) > 0:
+        elif conv1 == "pw_gate":
             # large planes: SE gate (plane means + FCs), then conv1 with the gate folded into the
             # per-sample weights and the bn1 partials in the epilogue (csrc/st_pw.hip)
             gate = self.se_block.gate(x, pool)
@@ -207,31 +208,23 @@ class SpectralTransform(nn.Module):
                       "ffc_pw_gate_conv")
         else:
             gate = self.se_block.gate(x, pool)
-            key = ("conv1", B, Cin, h2, w2, pool, str(dev))
-            ex = self._cache.get(key)
-            if ex is None:
-                seg = _plan.Seg("pw", Cin, h2, w2, pool=pool, gate=True)
-                ex = rt.ConvExec(B, c, [seg], [rt.conv_weight(self.conv1)], dev)
-                lp = rt.LaunchPlan([ex], dev)
-                self._cache[key] = ex = (ex, lp)
-            ex, lp = ex
-            ex.ensure_packed([rt.conv_weight(self.conv1)])
+            ex, lp = rt.cached_conv(self._cache, ("conv1", B, Cin, h2, w2, pool, str(dev)), B, c,
+                                    [_plan.Seg("pw", Cin, h2, w2, pool=pool, gate=True)], [rt.conv_weight(self.conv1)], dev)
             nrows = lp.stat_rows(0)
             slab = torch.empty((nrows, c, 4), device=dev, dtype=torch.float32) if use_batch else None
             lp.launch([ex.job([(x, gate)], t, stats=slab)], stream, flops=ex.flops)
-        # run_lfu: bn1 has two consumers (fu and the LFU gather), so it is finalized by its own launch
-        can_fold = use_batch and not self.run_lfu
-        fold = rt.bn_fold(self.bn1, c, slab, nrows, float(up * up), dev) if can_fold else None
-        if fold is None and can_fold:   # the staged FU's r2c can still fold it channel by channel
-            fold = rt.bn_fold_channels(self.bn1, c, slab, nrows, float(up * up), dev)
-        if fold is not None:   # bn1 finalized inside the FU's first kernel
-            return self.fu._run(t, up=up, in_relu=True, residual=True, in_fold=fold)
-        sc1, sh1 = rt.bn_scale_shift(self.bn1, c, slab, nrows if use_batch else 0, float(up * up), dev, stream)
-        if not self.run_lfu:
-            return self.fu._run(t, up=up, in_scale=sc1, in_shift=sh1, in_relu=True, residual=True)
-        ys = self._run_lfu(t, up, sc1, sh1)
-        v = self.fu._run(t, up=up, in_scale=sc1, in_shift=sh1, in_relu=True, residual=True)
-        return ag.lfu_tile_add_impl(v, ys, out=v)
+        # bn1 finalized inside the FU's first kernel where the route folds it (never with run_lfu: the LFU
+        # gather reads it too), else by its own launch
+        r = self.fu.route(B, c, h2 * up, w2 * up, up,
+                          rt.InBn(nrows, float(up * up), use_batch, self.bn1.momentum is None, self.run_lfu))
+        fold = sc1 = sh1 = None
+        if r.in_fold:
+            fold = rt.make_bn_fold(self.bn1, c, slab, nrows, float(up * up), dev, r.in_fold)
+        else:
+            sc1, sh1 = rt.bn_scale_shift(self.bn1, c, slab, nrows if use_batch else 0, float(up * up), dev, stream)
+        ys = self._run_lfu(t, up, sc1, sh1) if self.run_lfu else None
+        v = self.fu._launch(r, t, up, sc1, sh1, True, True, fold)
+        return v if ys is None else ag.lfu_tile_add_impl(v, ys, out=v)
 
     def forward(self, x, y=None):
         if y is not None:
@@ -249,14 +242,8 @@ class SpectralTransform(nn.Module):
         v = self.spectral(x)
         rt.sn_refresh(self.conv2)
         B, c, H, W = v.shape
-        key = ("conv2", B, c, H, W, str(v.device))
-        ex = self._cache.get(key)
-        if ex is None:
-            ex = rt.ConvExec(B, self.conv2.out_channels, [_plan.Seg("pw", c, H, W)], [rt.conv_weight(self.conv2)],
-                             v.device)
-            self._cache[key] = ex = (ex, rt.LaunchPlan([ex], v.device))
-        ex, lp = ex
-        ex.ensure_packed([rt.conv_weight(self.conv2)])
+        ex, lp = rt.cached_conv(self._cache, ("conv2", B, c, H, W, str(v.device)), B, self.conv2.out_channels,
+                                [_plan.Seg("pw", c, H, W)], [rt.conv_weight(self.conv2)], v.device)
         out = torch.empty((B, self.conv2.out_channels, H, W), device=v.device, dtype=torch.float32)
         lp.launch([ex.job([(v, None)], out)], rt.stream_of(v), flops=ex.flops)
         return out
