@@ -35,6 +35,7 @@ from .models import (CondDiscriminator32, DCGenerator32, Discriminator, Discrimi
                      FFCGenerator, FFCModel, FGanDiscriminator, FGenerator, FGenerator32, Generator32, Generator64)
 from .optim import FusedAdam, FusedAdamW
 from .resnet import DBlock, DBlockOptimized, GBlock, SNGANDiscriminator128, SNGANGenerator128
+from .sagan import SAGANDiscriminator, SAGANGenerator, SAGANSpectralNorm
 
 __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose", "FFC_BN_ACT", "SNFFC",
            "SNFFCTranspose", "spectral_norm_ffc", "set_sn_hip", "set_mix_precision", "set_lfu", "Resizer",
@@ -43,4 +44,5 @@ __all__ = ["FourierUnitSN", "SELayer", "SpectralTransform", "FFC", "FFCTranspose
            "Discriminator32", "FDiscriminator32", "GaussianNoise", "Config", "ConditionalBatchNorm2d", "set_cond_bn",
            "FCondGenerator32", "FCondGeneratorSTL", "CondDiscriminator32", "FCondDiscriminator32", "Self_Attn",
            "Generator32", "Generator64", "DCGenerator32", "aw_method", "GBlock", "DBlock", "DBlockOptimized",
-           "SNGANGenerator128", "SNGANDiscriminator128", "FusedAdamW", "FusedAdam"]
+           "SNGANGenerator128", "SNGANDiscriminator128", "FusedAdamW", "FusedAdam", "SAGANSpectralNorm",
+           "SAGANGenerator", "SAGANDiscriminator"]

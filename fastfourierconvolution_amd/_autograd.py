@@ -33,6 +33,7 @@ from __future__ import annotations
 
 import functools
 import json
+from typing import NamedTuple
 
 import torch
 import torch.nn as nn
@@ -861,10 +862,10 @@ class _StackedQKV:
         self.out_channels = self.weight.shape[0]
 
 
-def self_attn(mod, x):
+def self_attn(mod, x, need_attention=None):
     """Self_Attn ``mod`` on x (B, C, H, W) -> (out, attention or None): one stacked projection on the
-    pointwise GEMM (ffc::conv_layer), the fused attention (ffc::self_attn), and with mod.need_attention the
-    attention matrix (ffc::self_attn_matrix, no gradient)"""
+    pointwise GEMM (ffc::conv_layer), the fused attention (ffc::self_attn), and with mod.need_attention (or the
+    caller's ``need_attention`` for this call) the attention matrix (ffc::self_attn_matrix, no gradient)"""
     x = rt.require(x, "x")
     B, C, H, W = x.shape
     if C != mod.chanel_in:
@@ -875,7 +876,7 @@ def self_attn(mod, x):
     (qkv,) = conv_layer(B, [(M, 0, 0.0)], [(0, 0, _plan.Seg("pw", C, H, W), _StackedQKV(mod, grad))], [x])
     y, L, _ = torch.ops.ffc.self_attn(x, qkv, mod.gamma, grad)
     attention = None
-    if mod.need_attention:
+    if mod.need_attention if need_attention is None else need_attention:
         attention = torch.ops.ffc.self_attn_matrix(qkv.detach(), L.detach(), C)
     return y, attention
 
@@ -1251,6 +1252,9 @@ def cond_stem(mod, z, labels):
 
 
 # --------------------------------------------------------------------------- spectral norm
+SN_EPS_ADD = 1   # FFC_SN_EPS_ADD of include/ffc_amd.h: normalize(x) = x / (||x|| + eps)
+
+
 def sn_view(shape, dim):
     """(M, K, R, stride_m, stride_i) of SpectralNorm.reshape_weight_to_matrix read in place
     (ffc_sn_job): dim 0 is the dense (M, K) matrix, dim 1 of (d0, M, rest...) has
@@ -1296,14 +1300,17 @@ def _sn_check(ts, what, shapes=None):
             raise RuntimeError(f"spectral norm: {what} has {t.numel()} elements, expected {shapes[i]}")
 
 
-def sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training):
+def sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training, flags=None):
     """ffc::sn_weight: the spectral_norm pre-hook of len(w_orig) layers in one table (three launches in
     training mode, two in eval mode).  Writes w[i] = w_orig[i] / sigma[i], sigma (n,), in training
     mode u[i] / v[i] in place, and -- when ``saved`` is a flat tensor of sum(M + K) floats -- this
-    call's (u, v) of every layer into it, for the backward"""
+    call's (u, v) of every layer into it, for the backward.  ``flags``: ffc_sn_job.flags per layer
+    (SN_EPS_ADD: the SAGAN wrapper's x / (||x|| + eps)), None: 0 everywhere"""
     n = len(w_orig)
     if not (n and len(u) == len(v) == len(w) == len(dims) == n and sigma.numel() == n):
         raise RuntimeError("sn_weight: one (w_orig, u, v, w, dim) per layer and one sigma each")
+    if flags is not None and len(flags) != n:
+        raise RuntimeError("sn_weight: one flags word per layer (or none)")
     dev = w_orig[0].device
     jobs, ws = _sn_table(w_orig, dims, dev)
     _sn_check(w_orig, "weight_orig")
@@ -1318,6 +1325,7 @@ def sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training):
     for i, jb in enumerate(jobs):
         jb.w_orig, jb.u, jb.v, jb.w = ptr(w_orig[i]), ptr(u[i]), ptr(v[i]), ptr(w[i])
         jb.sigma = sigma.data_ptr() + 4 * i
+        jb.flags = int(flags[i]) if flags is not None else 0
         if saved.numel():
             jb.u_save, jb.v_save = pos, pos + 4 * jb.M
             pos += 4 * (jb.M + jb.K)
@@ -1350,32 +1358,53 @@ def sn_weight_bwd_impl(dw, w_orig, saved, sigma, dims):
     return out
 
 
+class SnLayer(NamedTuple):
+    """one layer of a SpectralNormWeight table (a plain (u, v, dim) tuple is taken as SnLayer(u, v, dim))"""
+    u: torch.Tensor          # buffers: constants for autograd, advanced in place
+    v: torch.Tensor
+    dim: int
+    flags: int = 0           # ffc_sn_job.flags (SN_EPS_ADD); the backward does not depend on it
+    live: bool = False       # the backward reads u and v as they stand when it runs, not this call's copies
+
+
 class SpectralNormWeight(torch.autograd.Function):
     """SpectralNorm.compute_weight for a list of layers: (weight_orig...) -> (weight...).  ``layers`` is
-    [(weight_u, weight_v, dim)] -- buffers, constants for autograd as in the hook, advanced in place in
-    training mode.  Saves weight_orig, sigma and this call's (u, v) (the kernels' own copies: the
+    [SnLayer] (or [(weight_u, weight_v, dim)]) -- buffers, constants for autograd as in the hook, advanced in
+    place in training mode.  Saves weight_orig, sigma and this call's (u, v) (the kernels' own copies: the
     buffers move on at the next forward, which may come before this backward, the reason the hook
-    clones them).  Backward: ffc::sn_weight_bwd over the whole list."""
+    clones them).  Backward: ffc::sn_weight_bwd over the whole list.  With ``live`` (the same for every layer of
+    a table) nothing is copied and the backward takes u and v as they then stand -- what the SAGAN wrapper's
+    graph does, which holds the Parameters themselves while every later forward replaces their data
+    (spectral.py:30-34); it costs one concatenation of the vectors per backward."""
 
     @staticmethod
     def forward(ctx, layers, training, *w_orig):
         src = [w.detach() for w in w_orig]
         src = [s if s.is_contiguous() else s.contiguous() for s in src]
-        dims = [int(d) for _, _, d in layers]
+        layers = [l if isinstance(l, SnLayer) else SnLayer(*l) for l in layers]
+        live = {bool(l.live) for l in layers}
+        if len(live) != 1:
+            raise NotImplementedError("spectral norm: the layers of one table save u / v alike")
+        live = live.pop()
+        flags = [int(l.flags) for l in layers]
+        dims = [int(l.dim) for l in layers]
         out = [torch.empty_like(s) for s in src]
         sigma = torch.empty(len(src), device=src[0].device, dtype=torch.float32)
-        need = any(ctx.needs_input_grad[2:])
-        saved = torch.empty(sum(u.numel() + v.numel() for u, v, _ in layers) if need else 0, device=src[0].device,
+        need = any(ctx.needs_input_grad[2:]) and not live
+        saved = torch.empty(sum(l.u.numel() + l.v.numel() for l in layers) if need else 0, device=src[0].device,
                             dtype=torch.float32)
-        torch.ops.ffc.sn_weight(src, [u for u, _, _ in layers], [v for _, v, _ in layers], out, sigma, saved, dims,
-                                bool(training))
+        torch.ops.ffc.sn_weight(src, [l.u for l in layers], [l.v for l in layers], out, sigma, saved, dims,
+                                bool(training), flags if any(flags) else None)
         ctx.dims = dims
+        ctx.live = [t for l in layers for t in (l.u, l.v)] if live else None
         ctx.save_for_backward(saved, sigma, *src)
         return tuple(out)
 
     @staticmethod
     def backward(ctx, *dws):
         saved, sigma, *src = ctx.saved_tensors
+        if ctx.live is not None:
+            saved = torch.cat([t.detach().reshape(-1) for t in ctx.live])
         dws = [g if g is not None else torch.zeros_like(s) for g, s in zip(dws, src)]
         grads = torch.ops.ffc.sn_weight_bwd(dws, src, saved, sigma, ctx.dims)
         return (None, None) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[2:]))

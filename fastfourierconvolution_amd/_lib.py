@@ -105,7 +105,7 @@ class SnJob(ctypes.Structure):
     """ffc_sn_job: one spectral-norm layer of ffc_sn_forward / ffc_sn_backward"""
     _fields_ = [("w_orig", c_void_p), ("u", c_void_p), ("v", c_void_p), ("w", c_void_p), ("sigma", c_void_p),
                 ("u_save", c_void_p), ("v_save", c_void_p), ("dw", c_void_p), ("dw_orig", c_void_p),
-                ("M", c_int), ("K", c_int), ("R", c_int), ("pad_", c_int),
+                ("M", c_int), ("K", c_int), ("R", c_int), ("flags", c_int),
                 ("stride_m", c_longlong), ("stride_i", c_longlong), ("ws_off", c_longlong)]
 
 

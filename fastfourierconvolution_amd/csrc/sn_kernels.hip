@@ -11,7 +11,8 @@
 //               for a chunk of 2048 columns; pb[cc][m] = sum_k Wm[m][k] p[k] over the chunk, one wave
 //               per row; the row-block-0 workgroups also write psq[cc] = sum p[k]^2 (fp64).
 //   C  scale  : every workgroup rebuilds nv = max(||p||, eps) from psq, t[m] = (sum_cc pb[cc][m]) / nv,
-//               nt = max(||t||, eps), sigma = sum_m (t[m] / nt) * t[m]; together the layer's
+//               nt = max(||t||, eps), sigma = sum_m (t[m] / nt) * t[m] (a job with flags bit 0: nv =
+//               ||p|| + eps, nt = ||t|| + eps, the l2normalize of the SAGAN wrapper); together the layer's
 //               workgroups write u = t / nt, v = p / nv (and the saved copies), workgroup 0 writes
 //               sigma, and each scales its 16384-element chunk: W = W_orig / sigma.
 //               v = normalize(p) and t = Wm v = (Wm p) / nv: the division commutes with the product, so
@@ -51,6 +52,7 @@ struct SnDev {
     float* pa;      // [nra][K]
     float* pb;      // [ncb][M]
     int M, K, R, stride_i;
+    int flags;      // ffc_sn_job.flags
     int vec;        // rows read by float4: R % 4 == 0, w_orig 16-byte aligned
     int evec;       // elementwise passes by float4: the tensors are 16-byte aligned
     int nra, nca, nrb, ncb, nchunk;
@@ -95,6 +97,13 @@ __device__ __forceinline__ int sn_col(const SnDev& j, int k) {
 }
 
 using ffc::block_sum_f64;   // sum over the workgroup, in every thread (ffc_internal.h)
+
+// the divisor of normalize(x) from ||x||^2: max(||x||, eps), or ||x|| + eps with FFC_SN_EPS_ADD.  The same
+// fp32 value in every workgroup of a layer: sq is merged in one fixed order
+__device__ __forceinline__ float sn_norm(double sq, int flags) {
+    const float n = (float)sqrt(sq);
+    return (flags & FFC_SN_EPS_ADD) ? n + SN_EPS : fmaxf(n, SN_EPS);
+}
 
 // ------------------------------------------------------------------ A: partial columns of Wm^T u
 __global__ __launch_bounds__(SN_THREADS) void sn_colsum_kernel(SnTable t) {
@@ -205,7 +214,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scale_kernel(SnTable t, int tra
     if (training) {
         double s = 0.0;
         for (int c = 0; c < j.ncb; ++c) s += j.psq[c];
-        nv = fmaxf((float)sqrt(s), SN_EPS);
+        nv = sn_norm(s, j.flags);
     }
     auto t_of = [&](int m) {
         double s = 0.0;
@@ -218,7 +227,7 @@ __global__ __launch_bounds__(SN_THREADS) void sn_scale_kernel(SnTable t, int tra
             const float tm = t_of(m);
             st += (double)tm * (double)tm;
         }
-        nt = fmaxf((float)sqrt(block_sum_f64(st, red)), SN_EPS);
+        nt = sn_norm(block_sum_f64(st, red), j.flags);
     }
     double sd = 0.0;
     for (int m = tid; m < M; m += SN_THREADS) {
@@ -376,6 +385,7 @@ const char* sn_build(const ffc_sn_job* jobs, int n, bool backward, void* ws, siz
         const bool dim0 = a.R == a.K && a.stride_m == a.K;
         const bool dim1 = a.R >= 1 && a.R < a.K && a.K % a.R == 0 && a.stride_m == a.R &&
                           a.stride_i == (long long)a.M * a.R;
+        if (a.flags & ~FFC_SN_EPS_ADD) return "unknown bit in flags";
         if (!dim0 && !dim1) return "unsupported matrix view (dim 0 or dim 1 of a dense weight)";
         if (a.ws_off < 0 || (a.ws_off & 15) || (size_t)a.ws_off > ws_bytes || ws_bytes - (size_t)a.ws_off < s.total)
             return "workspace too small (ffc_sn_ws_bytes per job, at ws_off)";
@@ -398,6 +408,7 @@ const char* sn_build(const ffc_sn_job* jobs, int n, bool backward, void* ws, siz
         d.M = a.M;
         d.K = a.K;
         d.R = a.R;
+        d.flags = a.flags;
         d.stride_i = dim0 ? a.M * a.K : (int)a.stride_i;
         d.vec = a.R % 4 == 0 && aligned16(a.w_orig);
         d.evec = backward ? aligned16(a.w_orig) && aligned16(a.dw) && aligned16(a.dw_orig)

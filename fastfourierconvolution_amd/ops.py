@@ -747,14 +747,15 @@ cbn_act.register_autograd(_cbn_act_bwd, setup_context=_cbn_act_setup)
 
 @torch.library.custom_op("ffc::sn_weight", mutates_args=("u", "v", "w", "sigma", "saved"))
 def sn_weight(w_orig: List[Tensor], u: List[Tensor], v: List[Tensor], w: List[Tensor], sigma: Tensor, saved: Tensor,
-              dims: List[int], training: bool) -> None:
+              dims: List[int], training: bool, flags: Optional[List[int]] = None) -> None:
     """w[i] <- w_orig[i] / sigma[i]; training: u[i], v[i] advanced in place by one power iteration;
-    saved: a flat copy of this call's (u, v) per layer, or an empty tensor"""
-    ag.sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training)
+    saved: a flat copy of this call's (u, v) per layer, or an empty tensor; flags: ffc_sn_job.flags per
+    layer (None: 0, the hook's normalize)"""
+    ag.sn_weight_impl(w_orig, u, v, w, sigma, saved, dims, training, flags)
 
 
 @sn_weight.register_fake
-def _(w_orig, u, v, w, sigma, saved, dims, training):
+def _(w_orig, u, v, w, sigma, saved, dims, training, flags=None):
     return None
 
 

@@ -110,3 +110,58 @@ def train_iteration(G, D, optim_G, optim_D, z_g, z_d, real, num_dis_updates=1, l
     for z in zs:
         loss_D = discriminator_step(G, D, optim_G, optim_D, z, real, labels=labels)
     return loss_G, loss_D
+
+
+def sagan_step(G, D, optim_G, optim_D, z_d, z_g, real, adv_loss='hinge'):
+    """benchmark_models/sagan/trainer.py:93-168 with ``adv_loss = 'hinge'``, over sagan.SAGANGenerator /
+    SAGANDiscriminator, in the reference's call order: both models in train mode;
+    D half: d_loss_real = relu(1 - D(real)).mean(), d_loss_fake = relu(1 + D(G(z_d))).mean(), both optimizers'
+    gradients reset, (d_loss_real + d_loss_fake).backward(), optim_D.step();
+    G half: g_loss = -D(G(z_g)).mean() on the updated critic, gradients reset, backward, optim_G.step().
+    -> (d_loss_real, d_loss_fake, g_loss), on the device.
+
+    One call runs D's spectral-norm wrappers three times and G's twice, so u and v advance that often, and G's
+    BatchNorm running statistics update in both halves, as in the reference.  Two things are not computed because
+    the reference throws them away: the D half runs G without recording its graph (the gradients d_loss.backward()
+    would leave in G are reset at :166 before anything reads them), and the G half does not accumulate the
+    critic's parameter gradients (they are reset at :125 of the next iteration); after the call D's ``.grad``s are
+    unset where the reference would hold those of g_loss.
+
+    ``adv_loss = 'wgan-gp'`` (the reference's default) raises NotImplementedError: its gradient penalty
+    differentiates a gradient of D, a double backward the custom ops do not have.  Takes torch's optimizers or
+    optim.FusedAdam (the reference: Adam, lr 1e-4 for G and 4e-4 for D, betas (0.0, 0.9), over the parameters
+    that require a gradient)."""
+    if adv_loss == 'wgan-gp':
+        raise NotImplementedError("sagan_step: adv_loss = 'wgan-gp' needs the gradient penalty, a double backward "
+                                  "through every layer of D that the custom ops do not have; use 'hinge'")
+    if adv_loss != 'hinge':
+        raise NotImplementedError(f"sagan_step: adv_loss = {adv_loss!r} ('hinge' only)")
+    D.train()
+    G.train()
+    d_out_real, _ = D(real)
+    d_loss_real = tF.relu(1.0 - d_out_real).mean()
+    with torch.no_grad():
+        fake_images, _ = G(z_d)
+    d_out_fake, _ = D(fake_images)
+    d_loss_fake = tF.relu(1.0 + d_out_fake).mean()
+    d_loss = d_loss_real + d_loss_fake
+    optim_D.zero_grad()
+    optim_G.zero_grad()
+    d_loss.backward()
+    optim_D.step()
+
+    fake_images, _ = G(z_g)
+    trained = [p for p in D.parameters() if p.requires_grad]
+    for p in trained:
+        p.requires_grad_(False)
+    try:
+        g_out_fake, _ = D(fake_images)
+    finally:
+        for p in trained:
+            p.requires_grad_(True)
+    g_loss_fake = -g_out_fake.mean()
+    optim_D.zero_grad()
+    optim_G.zero_grad()
+    g_loss_fake.backward()
+    optim_G.step()
+    return d_loss_real, d_loss_fake, g_loss_fake

@@ -768,7 +768,13 @@ int ffc_cbn_bwd_apply(const float* x, const float* dy, const int64_t* labels, co
  * Workspace: ffc_sn_ws_bytes(M, K) bytes per layer at byte offset ws_off (a multiple of 16) of ws;
  * 0 for M, K <= 0 or M * K >= 2^31.  16-byte accesses when R % 4 == 0 (rows) / the tensors are 16-byte
  * aligned (elementwise passes), 4-byte otherwise, in the same summation order: the results do not
- * depend on the alignment.  Pure additions: the ABI version is unchanged. */
+ * depend on the alignment.  Pure additions: the ABI version is unchanged.
+ * flags bit 0 (FFC_SN_EPS_ADD): normalize(x) = x / (||x||_2 + 1e-12) in both places, the l2normalize of the SAGAN
+ * baseline's SpectralNorm wrapper (benchmark_models/sagan/spectral.py:10-11), which also iterates in eval mode (the
+ * caller passes training = 1) and views ConvTranspose2d over dim 0.  The two forms agree bit for bit in fp32 once
+ * ||x|| is above about 6e-5.  A bit other than bit 0 is refused; the backward does not read flags.  The field took the
+ * place of a padding word that every caller zeroed: size and offsets of the struct are unchanged. */
+#define FFC_SN_EPS_ADD 1
 typedef struct ffc_sn_job {
     const float* w_orig;   /* M * K floats */
     float* u;              /* (M): read; written in training mode */
@@ -781,7 +787,7 @@ typedef struct ffc_sn_job {
     float* dw_orig;        /* backward only */
     int M, K;
     int R;
-    int pad_;
+    int flags;             /* FFC_SN_*; 0: the hook's normalize */
     long long stride_m, stride_i;
     long long ws_off;
 } ffc_sn_job;
