@@ -304,6 +304,13 @@ SIGNATURES = [
     ("ffc_pool2_act_bwd", c_int, [c_void_p, c_void_p, c_longlong, c_int, c_int, c_int, c_float, c_void_p, c_void_p]),
     ("ffc_relu_sum_pool", c_int, [c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
     ("ffc_relu_sum_pool_bwd", c_int, [c_void_p, c_void_p, c_longlong, c_int, c_void_p, c_void_p]),
+    ("ffc_feat_moments_state_doubles", c_size_t, [c_int]),
+    ("ffc_feat_moments_update", c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    ("ffc_kid_ws_doubles", c_size_t, [c_int, c_int]),
+    ("ffc_kid_sums", c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
+                             c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("ffc_isc_ws_doubles", c_size_t, [c_longlong, c_int, c_int]),
+    ("ffc_isc_sums", c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
 ]
 
 _lock = threading.Lock()

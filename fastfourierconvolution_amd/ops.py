@@ -53,6 +53,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from . import _autograd as ag
+from . import _metrics as mt
 from . import _plan
 from . import _runtime as rt
 
@@ -798,6 +799,45 @@ def aw_combine(g_real: List[Tensor], g_fake: List[Tensor], stats: Tensor, out: L
 @aw_combine.register_fake
 def _(g_real, g_fake, stats, out):
     return None
+
+
+# ---------------------------------------------------------------- ffc::feat_moments_update / kid_sums / isc_sums
+# torch_fidelity's FID / KID / Inception-score arithmetic from feature batches on csrc/metric_kernels.hip; the
+# callers are fidelity.FeatureStats, kid_features_to_metric and isc_features_to_metric.  Metrics carry no gradient.
+
+
+@torch.library.custom_op("ffc::feat_moments_update", mutates_args=("state",))
+def feat_moments_update(state: Tensor, features: Tensor) -> None:
+    """state [n, pivot[D], s1[D], S2[D][D]] (fp64) <- state + the batch ``features`` (B, D)"""
+    mt.feat_moments_update_impl(state, features)
+
+
+@feat_moments_update.register_fake
+def _(state, features):
+    return None
+
+
+@torch.library.custom_op("ffc::kid_sums", mutates_args=())
+def kid_sums(features_1: Tensor, features_2: Tensor, idx1: Tensor, idx2: Tensor, degree: int, gamma: float,
+             coef0: float) -> Tensor:
+    """-> (subsets, 6) fp64: [sum K_XX, sum diag K_XX, sum K_YY, sum diag K_YY, sum K_XY, trace K_XY]"""
+    return mt.kid_sums_impl(features_1, features_2, idx1, idx2, degree, gamma, coef0)
+
+
+@kid_sums.register_fake
+def _(features_1, features_2, idx1, idx2, degree, gamma, coef0):
+    return features_1.new_empty((idx1.shape[0], mt.KID_SUMS), dtype=torch.float64)
+
+
+@torch.library.custom_op("ffc::isc_sums", mutates_args=())
+def isc_sums(logits: Tensor, perm: Tensor, splits: int) -> Tensor:
+    """-> (splits, 4 + C) fp64 per chunk: [n_i, sum p log p, exponent, score, column sums of p]"""
+    return mt.isc_sums_impl(logits, perm, splits)
+
+
+@isc_sums.register_fake
+def _(logits, perm, splits):
+    return logits.new_empty((splits, mt.ISC_HEAD + logits.shape[1]), dtype=torch.float64)
 
 
 # ---------------------------------------------------------------- ffc::optim_step / ffc::optim_tick

@@ -941,6 +941,53 @@ int ffc_pool2_act_bwd(const float* y, const float* dy, long long P, int h, int w
 int ffc_relu_sum_pool(const float* x, long long P, int HW, float* out, void* stream);
 int ffc_relu_sum_pool_bwd(const float* x, const float* dout, long long P, int HW, float* dx, void* stream);
 
+/* ------------------------------------------------------------------ evaluation metrics from feature batches
+ * The arithmetic of torch_fidelity's FID, KID and Inception score (metric_fid.py:21-46, metric_kid.py:21-134,
+ * metric_isc.py:16-39) on fp32 row-major features / logits that are already on the device; the feature extractor
+ * is the caller's.  Every accumulation is fp64; matrix products run on v_mfma_f64_16x16x4_f64 with the operands
+ * converted from fp32 in registers.  No atomics, every sum in one fixed order: bitwise reproducible.  Nothing
+ * synchronises; every call can be captured into a graph.  fp32 pointers need 4-byte, int64 / fp64 pointers 8-byte
+ * alignment.  Pure additions: the ABI version is unchanged.
+ *
+ * ffc_feat_moments_update: the streaming scatter matrix of FID.  state (ffc_feat_moments_state_doubles(D) =
+ * 1 + 2 D + D^2 doubles, zero before the first call) = [n, pivot[D], s1[D], S2[D][D]] with
+ *   s1 = sum_rows (x - pivot)      S2 = sum_rows (x - pivot)(x - pivot)^T
+ * One call adds X (B, D), B >= 1, 1 <= D <= 2048.  The call that finds n == 0 sets pivot to its batch's fp64
+ * column mean; later calls read it.  Two launches: pivot / s1 (32 columns per workgroup), then S2: a workgroup
+ * per 64 x 64 tile of the upper triangle walks the whole batch, adds its tile in place and writes the mirrored
+ * element, so S2 is exactly symmetric; n <- n + B on the device.
+ *
+ * ffc_kid_sums: for each of `subsets` rows s of the int64 index tables idx1, idx2 (subsets, m), with
+ * X = F1[idx1[s]] (m, D), Y = F2[idx2[s]] and K(A, B) = (gamma A B^T + coef0)^degree (degree an integer >= 1, by
+ * repeated multiplication), sums (subsets, 6) =
+ *   [sum K_XX, sum diag K_XX, sum K_YY, sum diag K_YY, sum K_XY, trace K_XY]
+ * Two launches: a workgroup per (subset, pair, 64 x 64 tile) gathers its rows while staging and reduces its
+ * tile in the epilogue (XX and YY: the upper triangle of tiles, counted twice), then a workgroup per subset adds
+ * the partials in tile order.  No m x m matrix is written.  An index outside [0, N) forms no address and makes
+ * the six sums of its subset NaN.  ws: ffc_kid_ws_doubles(subsets, m) doubles.  m >= 2, 1 <= D <= 2048,
+ * subsets <= 65535.
+ *
+ * ffc_isc_sums: chunk i of `splits` is the rows perm[i N / splits .. (i + 1) N / splits) of logits (N, C),
+ * 1 <= C <= 1024, N >= splits.  With p = softmax(row) from an fp64 log-sum-exp, out (splits, 4 + C) per chunk =
+ *   [n_i, A = sum_rows sum_c p log p, E = (A - sum_c s_c log(s_c / n_i)) / n_i, exp(E), s[C]],  s_c = sum_rows p_c
+ * Two launches: a wave per row in one pass over the logits (128 rows per workgroup), then a workgroup per chunk.
+ * log(s_c / n_i) is taken as log1p(-t_c / n_i) from t_c = sum_rows (1 - p_c) where that is below 1/2, and
+ * 0 log 0 = 0.  A perm entry outside [0, N) forms no address and makes its chunk NaN.
+ * ws: ffc_isc_ws_doubles(N, C, splits) doubles.
+ *
+ * FFC_E_INVALID without a launch, the entry's name and the offending word in ffc_last_error(): a null or
+ * misaligned pointer, B < 1, D or C out of range, N1 or N2 < 1, m < 2, subsets or splits out of range,
+ * degree < 1, gamma or coef0 not finite, N < splits, N too large, a workspace too small. */
+size_t ffc_feat_moments_state_doubles(int D);
+int ffc_feat_moments_update(const float* X, int B, int D, double* state, void* stream);
+size_t ffc_kid_ws_doubles(int subsets, int m);
+int ffc_kid_sums(const float* F1, long long N1, const float* F2, long long N2, int D, const long long* idx1,
+                 const long long* idx2, int subsets, int m, int degree, double gamma, double coef0, double* ws,
+                 size_t ws_doubles, double* sums, void* stream);
+size_t ffc_isc_ws_doubles(long long N, int C, int splits);
+int ffc_isc_sums(const float* logits, long long N, int C, const long long* perm, int splits, double* ws,
+                 size_t ws_doubles, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
