@@ -311,6 +311,9 @@ SIGNATURES = [
                              c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
     ("ffc_isc_ws_doubles", c_size_t, [c_longlong, c_int, c_int]),
     ("ffc_isc_sums", c_int, [c_void_p, c_longlong, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    ("ffc_prc_ws_bytes", c_size_t, [c_longlong, c_longlong, c_int]),
+    ("ffc_prc", c_int, [c_void_p, c_longlong, c_void_p, c_longlong, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                        c_void_p, c_void_p, c_size_t, c_void_p]),
 ]
 
 _lock = threading.Lock()

@@ -1,5 +1,5 @@
-"""Host side of ffc::feat_moments_update, ffc::kid_sums and ffc::isc_sums (csrc/metric_kernels.hip): argument
-checks, workspaces and the launches.  Nothing here synchronises."""
+"""Host side of ffc::feat_moments_update, ffc::kid_sums and ffc::isc_sums (csrc/metric_kernels.hip) and of ffc::prc
+(csrc/prc_kernels.hip): argument checks, workspaces and the launches.  Nothing here synchronises."""
 from __future__ import annotations
 
 import torch
@@ -11,6 +11,8 @@ FM_MAX_D = 2048     # the widest layer torch_fidelity reads features from
 ISC_MAX_C = 1024
 KID_SUMS = 6        # [sum K_XX, sum diag K_XX, sum K_YY, sum diag K_YY, sum K_XY, trace K_XY]
 ISC_HEAD = 4        # [n_i, sum p log p, exponent, score] in front of the column sums
+PRC_MAX_D = 4096    # VGG-16 fc2_relu, torch_fidelity's default layer for PRC
+PRC_MAX_NEIGHBORHOOD = 7
 
 
 def state_doubles(D: int) -> int:
@@ -59,6 +61,34 @@ def kid_sums_impl(f1, f2, idx1, idx2, degree, gamma, coef0):
                              int(degree), float(gamma), float(coef0), ptr(ws), nws, ptr(sums), rt.stream_of(f1)),
               "ffc_kid_sums")
     return sums
+
+
+def prc_impl(f1, f2, neighborhood):
+    """-> (radii2_1 (N1,), radii2_2 (N2,), hit_2 (N2,) int32, hit_1 (N1,) int32, counts (2,)) of ffc_prc"""
+    f1, f2 = _features(f1, "prc: features_1"), _features(f2, "prc: features_2")
+    if f1.shape[1] != f2.shape[1] or f1.device != f2.device:
+        raise ValueError("prc: the two feature matrices need one width and one device")
+    k = int(neighborhood)
+    (N1, D), N2 = f1.shape, f2.shape[0]
+    if not 1 <= k <= PRC_MAX_NEIGHBORHOOD:
+        raise ValueError(f"prc: neighborhood = {k} out of range (1 .. {PRC_MAX_NEIGHBORHOOD})")
+    if D > PRC_MAX_D:
+        raise ValueError(f"prc: D = {D} > {PRC_MAX_D}")
+    if min(N1, N2) < k + 1:
+        raise ValueError(f"prc: N1 = {N1}, N2 = {N2} rows cannot hold {k + 1} neighbours")
+    L = rt.lib()
+    nws = L.ffc_prc_ws_bytes(N1, N2, k)
+    if nws == 0:
+        raise ValueError(f"prc: N1 = {N1} or N2 = {N2} too large")
+    dev = f1.device
+    ws = torch.empty(nws // 8, device=dev, dtype=torch.float64)
+    r1, r2 = torch.empty(N1, device=dev, dtype=torch.float64), torch.empty(N2, device=dev, dtype=torch.float64)
+    hit_2, hit_1 = torch.empty(N2, device=dev, dtype=torch.int32), torch.empty(N1, device=dev, dtype=torch.int32)
+    counts = torch.empty(2, device=dev, dtype=torch.float64)
+    with rt.observe("prc", flops=2.0 * D * (N1 * N1 + N2 * N2 + N1 * N2)):
+        check(L.ffc_prc(ptr(f1), N1, ptr(f2), N2, D, k, ptr(r1), ptr(r2), ptr(hit_2), ptr(hit_1), ptr(counts), ptr(ws),
+                        nws, rt.stream_of(f1)), "ffc_prc")
+    return r1, r2, hit_2, hit_1, counts
 
 
 def isc_sums_impl(logits, perm, splits):

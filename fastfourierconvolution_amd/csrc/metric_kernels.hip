@@ -15,19 +15,22 @@
 // Every sum has a fixed place in a fixed order (k ascending inside a tile, lanes by xor shuffles, waves in order,
 // partials by index): no atomics, results are bitwise reproducible and independent of the device's CU count.
 //
-// fp64 MFMA fragment maps (16x16x4): A[i = lane & 15][k = lane >> 4], B[k = lane >> 4][j = lane & 15], one double
-// each; C/D register r of lane l is row (l >> 4) + 4 r, column l & 15 -- not the f32 map.
+// The fp64 MFMA tile loop (mma_chunk, zero_acc) and its fragment maps are in mfma_f64_tile.h.
 #include "ffc_internal.h"
+#include "mfma_f64_tile.h"
 
 #include <cmath>
 
 namespace {
 
-typedef double doublex4 __attribute__((ext_vector_type(4)));
+using ffc::block_sum_f64;
+using ffc::mma_chunk;
+using ffc::MT_KC;
+using ffc::wave_sum_f64;
+using ffc::zero_acc;
 
 constexpr int MT_THREADS = 256;
 constexpr int MT_TILE = 64;      // output tile side of a workgroup (moments S2, KID Gram)
-constexpr int MT_KC = 32;        // k per staged chunk
 constexpr int FM_LD = MT_TILE + 8;   // moments LDS image [k][column]: 72 doubles per k row
 constexpr int KID_LD = MT_KC + 4;    // KID LDS image [row][k]: 36 doubles per row
 constexpr int FM_COLS = 32, FM_GROUPS = 8;   // kernel A of the moments
@@ -35,32 +38,6 @@ constexpr int ISC_CPL = 16;      // logits columns per lane: C <= 1024
 constexpr int ISC_ROWS = 128;    // rows per workgroup
 constexpr int ISC_MAX_C = 64 * ISC_CPL;
 constexpr int FM_MAX_D = 2048;
-
-using ffc::block_sum_f64;
-using ffc::wave_sum_f64;
-
-// one staged chunk of MT_KC k on the wave's 2 x 2 tiles; element (i, k) of an operand image is at i * SI + k * SK
-template <int SI, int SK>
-__device__ __forceinline__ void mma_chunk(const double* As, const double* Bs, int wi, int wj, doublex4 (&acc)[2][2]) {
-    const int lane = threadIdx.x & 63, e = lane & 15, kq = lane >> 4;
-#pragma unroll
-    for (int kk = 0; kk < MT_KC; kk += 4) {
-        const int k = kk + kq;
-        const double a0 = As[(wi + e) * SI + k * SK], a1 = As[(wi + 16 + e) * SI + k * SK];
-        const double b0 = Bs[(wj + e) * SI + k * SK], b1 = Bs[(wj + 16 + e) * SI + k * SK];
-        acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, acc[0][0], 0, 0, 0);
-        acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, acc[0][1], 0, 0, 0);
-        acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, acc[1][0], 0, 0, 0);
-        acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, acc[1][1], 0, 0, 0);
-    }
-}
-
-__device__ __forceinline__ void zero_acc(doublex4 (&acc)[2][2]) {
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-        for (int b = 0; b < 2; ++b) acc[a][b] = doublex4{0.0, 0.0, 0.0, 0.0};
-}
 
 // ------------------------------------------------------------------ moments A: pivot and s1
 // state = [n, pivot[D], s1[D], S2[D][D]]

@@ -21,6 +21,9 @@ caller's; the metric arithmetic that works on feature tensors runs on the device
                            scatter matrix on the device; ``fid_statistics_to_metric`` metric_fid.py:32-46
   * ``kid_features_to_metric``  metric_kid.py:21-134 (polynomial kernel, ``mmd_est="unbiased"``)
   * ``isc_features_to_metric``  metric_isc.py:16-39
+  * ``prc_features_to_metric``  metric_prc.py:57-94 (csrc/prc_kernels.hip); ``calculate_prc`` drives
+                           a generator into it.  The reference's trainers do not pass ``prc=True``; this
+                           completes the vendored evaluation surface
   * ``calculate_metrics``  metrics.py's driver for a generator as input 1, with the caller's extractor
 """
 from __future__ import annotations
@@ -31,7 +34,7 @@ import torch.nn as nn
 
 __all__ = ["random_normal", "GenerativeModelModuleWrapper", "generate_batches", "FeatureStats",
            "fid_statistics_to_metric", "kid_features_to_metric", "isc_features_to_metric", "calculate_metrics",
-           "mmd2_from_sums", "isc_from_chunk_sums"]
+           "mmd2_from_sums", "isc_from_chunk_sums", "prc_features_to_metric", "calculate_prc"]
 
 DEFAULT_BATCH_SIZE = 64     # torch_fidelity/defaults.py:5
 DEFAULT_RNG_SEED = 2020     # torch_fidelity/defaults.py:56
@@ -105,6 +108,9 @@ KEY_METRIC_ISC_MEAN = "inception_score_mean"
 KEY_METRIC_ISC_STD = "inception_score_std"
 KEY_METRIC_KID_MEAN = "kernel_inception_distance_mean"
 KEY_METRIC_KID_STD = "kernel_inception_distance_std"
+KEY_METRIC_PRECISION = "precision"
+KEY_METRIC_RECALL = "recall"
+KEY_METRIC_F_SCORE = "f_score"
 
 
 def _repivot(n, pivot, s1, S2, new_pivot):
@@ -268,6 +274,55 @@ def isc_features_to_metric(logits, splits=10, shuffle=True, rng_seed=DEFAULT_RNG
     out = torch.ops.ffc.isc_sums(logits, torch.from_numpy(perm.astype(np.int64)).to(logits.device), splits)
     scores = out[:, 3]
     return {KEY_METRIC_ISC_MEAN: float(scores.mean().item()), KEY_METRIC_ISC_STD: float(scores.std(unbiased=False).item())}
+
+
+PRC_MAX_NEIGHBORHOOD = 7
+
+
+def prc_features_to_metric(features_1, features_2, prc_neighborhood=3, prc_batch_size=10000, save_cpu_ram=False) -> dict:
+    """metric_prc.py:57-94: the improved precision and recall of Kynkaanniemi et al.  **Convention:
+    ``features_1`` is the REAL set, ``features_2`` the GENERATED one** (metric_prc.py:70).  One call of ffc::prc:
+    squared distances in fp64 on the device, no N x N matrix anywhere; precision = (samples of features_2 inside
+    some k-NN ball of features_1) / N2, recall = (samples of features_1 inside some ball of features_2) / N1 from
+    the exact integer counts, f_score = 2 p r / max(1e-5, p + r).  ``prc_batch_size`` and ``save_cpu_ram`` are
+    accepted and ignored: both routes of the reference give one result, and neither of their matrices exists
+    here.  ValueError where the reference asserts, for a neighborhood outside 1 .. 7 and for fewer than
+    neighborhood + 1 rows (where the reference's kthvalue fails).  Features must be finite."""
+    if not (torch.is_tensor(features_1) and features_1.dim() == 2 and torch.is_tensor(features_2)
+            and features_2.dim() == 2 and features_1.shape[1] == features_2.shape[1]):
+        raise ValueError("features must be two 2-D tensors of one width")
+    k = prc_neighborhood
+    if type(k) is not int or not 1 <= k <= PRC_MAX_NEIGHBORHOOD:
+        raise ValueError(f"prc_neighborhood must be an integer in 1 .. {PRC_MAX_NEIGHBORHOOD}")
+    n1, n2 = len(features_1), len(features_2)
+    if min(n1, n2) < k + 1:
+        raise ValueError(f"PRC neighborhood {k} needs at least {k + 1} samples (input_1: {n1}, input_2: {n2})")
+    counts = torch.ops.ffc.prc(features_1, features_2, k)[4].cpu()
+    precision, recall = float(counts[0]) / n2, float(counts[1]) / n1
+    return {KEY_METRIC_PRECISION: precision, KEY_METRIC_RECALL: recall,
+            KEY_METRIC_F_SCORE: 2 * precision * recall / max(1e-5, precision + recall)}
+
+
+def calculate_prc(gen_model, feature_extractor, num_samples, real_features, batch_size=DEFAULT_BATCH_SIZE,
+                  rng_seed=DEFAULT_RNG_SEED, prc_neighborhood=3) -> dict:
+    """Precision and recall of a generator against ``real_features`` (N1, D), with the caller's feature
+    extractor (torch_fidelity's default for PRC is VGG-16 ``fc2_relu``, D = 4096; its weights come by URL).
+    ``feature_extractor(images_uint8) -> features_2d`` (or a tuple whose first entry they are, as
+    ``calculate_metrics`` takes) is called on every batch of ``generate_batches``; then
+    ``prc_features_to_metric(real_features, generated)``, that function's documented convention.
+
+    The reference's own driver (metric_prc.py:104-112) puts input 1 first whatever it is: with a generator as
+    input 1, as its trainers pass one to ``calculate_metrics``, what it reports as "precision" is this
+    function's "recall" and the other way round."""
+    if not (torch.is_tensor(real_features) and real_features.dim() == 2):
+        raise ValueError("real_features must be a 2-D feature tensor")
+    feats = []
+    for images in generate_batches(gen_model, num_samples, batch_size, True, rng_seed):
+        f = feature_extractor(images)
+        if isinstance(f, (tuple, list)):
+            f = f[0]
+        feats.append(f.float().contiguous())
+    return prc_features_to_metric(real_features, torch.cat(feats), prc_neighborhood=prc_neighborhood)
 
 
 def _stats_of(input2, dim):

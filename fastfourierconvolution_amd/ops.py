@@ -840,6 +840,26 @@ def _(logits, perm, splits):
     return logits.new_empty((splits, mt.ISC_HEAD + logits.shape[1]), dtype=torch.float64)
 
 
+# ---------------------------------------------------------------- ffc::prc
+# torch_fidelity's improved precision and recall (metric_prc.py) from two feature matrices on csrc/prc_kernels.hip;
+# the caller is fidelity.prc_features_to_metric.  No gradient.
+
+
+@torch.library.custom_op("ffc::prc", mutates_args=())
+def prc(features_1: Tensor, features_2: Tensor, neighborhood: int) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    """-> (radii2_1 (N1,) fp64, radii2_2 (N2,) fp64, hit_2 (N2,) int32, hit_1 (N1,) int32, counts (2,) fp64 =
+    [sum hit_2, sum hit_1]); features_1 is the real set"""
+    return mt.prc_impl(features_1, features_2, neighborhood)
+
+
+@prc.register_fake
+def _(features_1, features_2, neighborhood):
+    n1, n2 = features_1.shape[0], features_2.shape[0]
+    return (features_1.new_empty((n1,), dtype=torch.float64), features_1.new_empty((n2,), dtype=torch.float64),
+            features_1.new_empty((n2,), dtype=torch.int32), features_1.new_empty((n1,), dtype=torch.int32),
+            features_1.new_empty((2,), dtype=torch.float64))
+
+
 # ---------------------------------------------------------------- ffc::optim_step / ffc::optim_tick
 # torch.optim's single-tensor Adam / AdamW and LambdaLR(lambda s: 1 - s / T).step() on csrc/optim_kernels.hip, the
 # step and schedule counts in ``state`` on the device; the optimizers are optim.FusedAdamW / FusedAdam

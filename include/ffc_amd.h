@@ -988,6 +988,31 @@ size_t ffc_isc_ws_doubles(long long N, int C, int splits);
 int ffc_isc_sums(const float* logits, long long N, int C, const long long* perm, int splits, double* ws,
                  size_t ws_doubles, double* out, void* stream);
 
+/* ------------------------------------------------------------------ precision and recall from two feature sets
+ * The improved precision and recall of torch_fidelity's metric_prc.py:57-66 (Kynkaanniemi et al.) on fp32
+ * row-major features F1 (N1, D), the REAL set, and F2 (N2, D) that are already on the device.  With k =
+ * neighborhood and d2(a, b) = |a - b|^2:
+ *   radii2_1[j] = the (k + 1)-th smallest of d2(F1[j], F1[.]) over all rows of F1, the row itself included
+ *                 (kthvalue(k + 1) of the full matrix); radii2_2[i] alike over F2
+ *   hit_2[i] = any_j d2(F2[i], F1[j]) <= radii2_1[j]        precision = mean(hit_2) = counts[0] / N2
+ *   hit_1[j] = any_i d2(F1[j], F2[i]) <= radii2_2[i]        recall    = mean(hit_1) = counts[1] / N1
+ * Squared distances throughout, no square root, compared with <=: d2 = max(0, n_i + n_j - 2 g_ij) with the fp64 row
+ * norms n and g from v_mfma_f64_16x16x4_f64 on operands converted from fp32 while staged; no centring, the
+ * cancellation costs at most (D + 8) 2^-53 sum_k (|a_k| + |b_k|)^2 per pair.  Seven launches: norms (a wave per row;
+ * it also zeroes the flags), per set the strips' k + 1 smallest per row and their merge, one pass over the cross
+ * product for both flag arrays, the counts (exact integers as doubles).  Nothing N x N is allocated: ws holds the
+ * norms and the candidates of one set's column strips (1024 columns each), ffc_prc_ws_bytes(N1, N2, neighborhood)
+ * bytes, 0 for arguments out of range.  No atomics; radii, flags and counts are bitwise reproducible.  Nothing
+ * synchronises; the call can be captured into a graph.  hit_2, hit_1: int (4-byte aligned), written 0 or 1.
+ * Limits: 1 <= D <= 4096, 1 <= neighborhood <= 7, N1, N2 >= neighborhood + 1 and at most 64 * 65535 rows.  The
+ * features must be finite: rows with NaN or Inf are outside the contract.  Pure additions: the ABI version is
+ * unchanged.
+ * FFC_E_INVALID without a launch: a null or misaligned pointer, D, neighborhood, N1 or N2 out of range, a workspace
+ * too small. */
+size_t ffc_prc_ws_bytes(long long N1, long long N2, int neighborhood);
+int ffc_prc(const float* F1, long long N1, const float* F2, long long N2, int D, int neighborhood, double* radii2_1,
+            double* radii2_2, int* hit_2, int* hit_1, double* counts, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
